@@ -11,9 +11,15 @@ across ranks (weak scaling).  Prints ONE JSON line on rank 0.
 `--gpus N` with N > 1 and no RANK in the environment re-launches this script as N ranks
 (torch.distributed.run, one process per GPU) before anything touches the GPU.
 
-At N = 1 the line also carries the other BASELINE configs measured on this GPU ("configs": C1 Item table,
-C2 moments, C3 HLL + Compliance, C4 correlations + moments, each at its BASELINE size) and the CPU
-baselines (the oracle's C restatement on this host's CPU share).
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the headline line.
+`--full` adds everything else: at N = 1 the other BASELINE configs measured on this GPU ("configs": C1 Item
+table, C2 moments, C3 HLL + Compliance, C4 correlations + moments, each at its BASELINE size), the CPU
+baselines (the oracle's C restatement on this host's CPU share), the per-kernel hipEvent timing of the steps
+and the roofline of the dominant kernel, plan-creation timing, state I/O and the Arrow ingestion leg.
+
+`--dump-outputs DIR` writes what the last timed step returned (the per-analyzer state slot sets after the
+incremental append, and the metrics they decode to) as DIR/<name>.npy.  The tables are generated from a
+fixed seed, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -51,6 +57,12 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: per-kernel timing + roofline, plan-creation "
+                        "timing, state I/O, the ingestion leg, the --configs and the CPU baselines (the options "
+                        "below that size or switch those legs act only with --full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (state slot sets, metrics) as DIR/<name>.npy")
     p.add_argument("--rows", type=int, default=1_000_000_000, help="rows per GPU")
     p.add_argument("--chunk", type=int, default=DEFAULT_CHUNK, help="rows per chunk")
     p.add_argument("--cpu-sample", type=int, default=62_500_000, help="rows timed on the CPU baseline (0 = skip)")
@@ -69,7 +81,12 @@ def parse(argv=None):
                    help="skip the fresh-process plan-creation timing (C3 / C5, cold and warm JIT cache)")
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                    help="process group for N > 1 (nccl = RCCL over xGMI; gloo: launcher tests with ranks sharing a GPU)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.skip_headline and not args.full:
+        p.error("--skip-headline measures only the --configs, which run with --full")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -163,8 +180,8 @@ def main():
     if world_env != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} disagrees with WORLD_SIZE={world_env}")
     rank = int(os.environ.get("RANK", "0"))
-    plan_ms = (plan_create_timing() if (rank == 0 and world_env == 1 and args.plan_timing and not args.skip_headline)
-               else None)
+    plan_ms = (plan_create_timing() if (args.full and rank == 0 and world_env == 1 and args.plan_timing
+                                        and not args.skip_headline) else None)
     import torch
     import torch.distributed as dist
 
@@ -225,13 +242,16 @@ def main():
     # only when the pool is empty); enabling again below zeroes the counters and keeps the pool
     # the collector runs (and is then switched off, as timeit does) before the warm-up, not between it and
     # the timed steps: a ~50 ms idle GPU there drops its clocks and the first timed step ran ~7 % slower
-    plan.enable_timing(True)
+    # (--full only: a plain run records no per-kernel events)
+    if args.full:
+        plan.enable_timing(True)
     gc.collect()
     gc.disable()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    plan.enable_timing(True)
+    if args.full:
+        plan.enable_timing(True)
     host_ms.update(merge=0.0, append=0.0)
     if world > 1:
         dist.barrier()
@@ -244,7 +264,7 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    kernels = kernel_report(plan, chunks, n_total)
+    kernels = kernel_report(plan, chunks, n_total) if args.full else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -252,9 +272,6 @@ def main():
 
     rows_all = n_total * world * args.steps
     value = rows_all / elapsed
-    dom_name, dom = max(((k, v) for k, v in kernels.items() if k.startswith("dq_column_scan")),
-                        key=lambda kv: kv[1]["ms_total"])
-    traffic = pmc_traffic(dom["pmc_name"]) if chunk == DEFAULT_CHUNK else None
     out = {
         "metric": "rows/sec (whole node) for fused 16-col profile scan; % of HBM peak BW",
         "value": value,
@@ -276,17 +293,21 @@ def main():
         "hbm_frac_of_step": (algo_bytes_per_step / (elapsed / args.steps)) / 1e9 / HBM_PEAK_GBS,
         "rank_merge_ms_per_step": host_ms["merge"] / args.steps if world > 1 else 0.0,
         "append_ms_per_step": host_ms["append"] / args.steps,
-        "roofline": roofline(dom_name, dom, traffic, kernels),
-        "cpu_baseline": None,
-        "plan_create_ms": plan_ms,
     }
-    if rank == 0 and world == 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, analyzers, persisted[0])
+    if args.full:
+        dom_name, dom = max(((k, v) for k, v in kernels.items() if k.startswith("dq_column_scan")),
+                            key=lambda kv: kv[1]["ms_total"])
+        traffic = pmc_traffic(dom["pmc_name"]) if chunk == DEFAULT_CHUNK else None
+        out.update(roofline=roofline(dom_name, dom, traffic, kernels), cpu_baseline=None, plan_create_ms=plan_ms)
+    if args.full and rank == 0 and world == 1:
         out["state_io"] = state_io_timing(analyzers, persisted[0])
     # the CPU baselines run after every GPU measurement (their host copies are taken now): OpenMP's worker
     # threads outlive a parallel region, and config steps timed after one showed 39-64 ms outliers among
     # 22.5 ms C3 steps (none with the baseline off or run last)
     deferred_cpu = []
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         n_cpu = min(args.cpu_sample, chunks[0].num_rows)
         cols_cpu = _host_cols(chunks[0], n_cpu)
         deferred_cpu.append(lambda: out.__setitem__("cpu_baseline", cpu_baseline(cols_cpu, n_cpu, args.cpu_threads,
@@ -294,10 +315,10 @@ def main():
     plan.close()
     del chunks
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.ingest_rows > 0:
+    if args.full and rank == 0 and world == 1 and args.ingest_rows > 0:
         out["ingest"] = ingest_timing(args, analyzers)
         torch.cuda.empty_cache()
-    if world == 1 and args.configs:
+    if args.full and world == 1 and args.configs:
         out["configs"] = {}
         for cfg in [c for c in re.split(r"[,+]", args.configs) if c]:
             out["configs"][cfg] = run_config(cfg, args, deferred_cpu)
@@ -308,6 +329,33 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, analyzers, states) -> None:
+    """What the timed path returned in its last step, as float arrays in analyzer order:
+    metrics.npy       float64 [analyzers]: the metric each state decodes to (NaN for an empty state)
+    state_fields.npy  float64: the fields of every non-HLL state, concatenated (counts are exact below 2^53)
+    hll_words.npy     float32 [ApproxCountDistinct analyzers, 52 x 4]: the 16-bit quarters, low first, of each
+                      HLL state's 52 register words (exact)"""
+    import dataclasses
+
+    import numpy as np
+
+    metrics, fields, hll = [], [], []
+    for a, s in zip(analyzers, states):
+        st = a._from_result(s)
+        m = a.computeMetricFrom(st)
+        metrics.append(m.value.get() if m.value.isSuccess else float("nan"))
+        for f in dataclasses.fields(st) if st is not None else ():
+            v = getattr(st, f.name)
+            if f.name == "words":
+                hll.append(np.array(v, dtype=np.int64).view(np.uint16).astype(np.float32))
+            else:
+                fields.append(float(v))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "metrics.npy"), np.array(metrics, dtype=np.float64))
+    np.save(os.path.join(directory, "state_fields.npy"), np.array(fields, dtype=np.float64))
+    np.save(os.path.join(directory, "hll_words.npy"), np.array(hll, dtype=np.float32).reshape(len(hll), -1))
 
 
 def kernel_report(plan, chunks, n_total) -> dict:

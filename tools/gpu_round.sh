@@ -5,7 +5,7 @@
 #   suite            the whole GPU test suite (pytest -m gpu)
 #   test=PATHS       pytest over PATHS (comma-separated, e.g. tests/test_plan_split.py,tests/test_pair_lane.py)
 #   smoke            __graft_entry__.smoke()
-#   bench[=ARGS]     python bench.py ARGS (ARGS with ',' for spaces) -> TAG_bench.json
+#   bench[=ARGS]     python bench.py ARGS (ARGS with ',' for spaces; --full for the whole line) -> TAG_bench.json
 #   prof             tools/profile_round.sh TAG (kernel trace + FETCH + SQ passes of the default bench)
 #   pmc5             tools/pmc_c5.sh TAG (SQ counter passes of the C5 headline kernels)
 #   clock            tools/clock_probe.sh TAG (held clock under the headline kernels)

@@ -6,7 +6,7 @@ TAG=${1:-pmccfg}
 CFG=${2:-c3}
 LIB=${3:-deequ_amd/libdqscan.so}
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"; mkdir -p gpurun_out; export TMPDIR=/tmp
-B="bench.py --skip-headline --configs=$CFG --config-rows 250000000 --config-steps 1 --cpu-sample 0 --ingest-rows 0"
+B="bench.py --full --skip-headline --configs=$CFG --config-rows 250000000 --config-steps 1 --cpu-sample 0 --ingest-rows 0"
 P1="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 P2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VSKIPPED"
 P3="GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS_ATOMIC"
