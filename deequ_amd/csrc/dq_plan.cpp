@@ -190,6 +190,12 @@ static bool pow10_i64(int s, int64_t& out) {
   return true;
 }
 
+// floor(u / p) for p > 0, without the overflow of -u + p - 1 near INT64_MIN
+static int64_t floor_div(int64_t u, int64_t p) {
+  const int64_t q = u / p;
+  return (u % p != 0 && u < 0) ? q - 1 : q;
+}
+
 // exact compare of two non-double literals: returns -1/0/1
 static int exact_cmp(const Lit& a, const Lit& b) {
   int64_t pa = 1, pb = 1;
@@ -347,7 +353,7 @@ struct Lowering {
       int64_t p10;
       pow10_i64(t - sc, p10);
       const int64_t u = lit.i;
-      const int64_t fl = u >= 0 ? u / p10 : -((-u + p10 - 1) / p10);
+      const int64_t fl = floor_div(u, p10);
       const bool exact = (u % p10) == 0;
       const int64_t ce = exact ? fl : fl + 1;
       switch (cmp) {
@@ -398,7 +404,21 @@ struct Lowering {
     return DQ_OK;
   }
 
-  // column CMP literal, with Spark 2.2 coercions (integral vs decimal exact, anything vs double in double)
+  // column CMP literal, or COALESCE(column, fallback) CMP literal, with Spark 2.2's coercions.  The operand's type
+  // comes first: the column's, widened by the fallback (COALESCE takes the common type of its arguments); then
+  // the comparison's type from the operand and the literal:
+  //   integral operand (integral column, fallback NULL / integer / decimal): vs an integer or decimal literal
+  //     exact, vs a double literal in double;
+  //   an integral column with a double fallback is a DoubleType operand: every literal is cast to double and the
+  //     column compares as (double)value, also against an integer or decimal literal;
+  //   FloatType operand (float column, fallback NULL / integer, the integer cast to float): vs an integer literal
+  //     in float (the literal rounded to float: findTightestCommonType), vs a decimal literal of any scale or a
+  //     double literal in double (DecimalPrecision: the decimal cast to double);
+  //   a float column with a decimal or double fallback is a DoubleType operand: every literal is cast to double, an
+  //     integer one too (not rounded to float);
+  //   DoubleType column: the fallback and the literal cast to double.
+  // A float widens to double exactly, so every float case is a double compare with the literal rounded as above.
+  // null_res is the comparison of the fallback, widened the same way, with the literal.
   dq_status emit_col_lit(const Operand& o, int cmp, Lit lit) {
     const dq_column_desc& cd = (*schema)[o.col];
     if (is_decimal(cd.type)) return emit_dec_lit(o, cmp, lit, cd.type);
@@ -415,17 +435,18 @@ struct Lowering {
         return set_error(DQ_E_UNSUPPORTED, "boolean column compared with a non-boolean literal");
       if (lit.k == Lit::BOOL) lit.k = Lit::INT;
       if (fb.k == Lit::BOOL) fb.k = Lit::INT;
-    } else if (cd.type == DQ_TYPE_F32) {
-      // FloatType vs an integral literal compares in FloatType (the literal cast to float: findTightestCommonType);
-      // vs a decimal or double literal in DoubleType (DecimalPrecision: the decimal cast to double) -- the float
-      // widens to double exactly, so every case is a double compare with the literal rounded accordingly.  A
-      // COALESCE(col, lit) fallback takes the operand's widened type the same way.
-      auto as_float_cmp = [](Lit& l) {
-        if (l.k == Lit::INT || (l.k == Lit::DEC && l.scale == 0)) { l.d = int_as_float(l.i); l.k = Lit::DBL; }
-        else if (l.k == Lit::DEC) { l.d = lit_to_double(l); l.k = Lit::DBL; }
+    } else {
+      const bool fb_wide = o.has_fallback && (fb.k == Lit::DBL || (fb.k == Lit::DEC && cd.type == DQ_TYPE_F32));
+      const bool dbl_operand = cd.type == DQ_TYPE_F64 || fb_wide;
+      auto widen = [](Lit& l, bool in_float) {  // an integer or decimal literal as the double it compares as
+        if (l.k != Lit::INT && l.k != Lit::DEC) return;
+        l.d = in_float && l.k == Lit::INT ? int_as_float(l.i) : lit_to_double(l);
+        l.k = Lit::DBL;
       };
-      as_float_cmp(lit);
-      if (o.has_fallback) as_float_cmp(fb);
+      if (is_floating(cd.type) || dbl_operand) {
+        if (o.has_fallback) widen(fb, cd.type == DQ_TYPE_F32);
+        widen(lit, cd.type == DQ_TYPE_F32 && !dbl_operand);
+      }
     }
     p.null_res = o.has_fallback ? lit_cmp_result(cmp, fb, lit) : NR_NULL;
     if (lit.k == Lit::NUL) { push_const(NR_NULL); return DQ_OK; }
@@ -439,7 +460,7 @@ struct Lowering {
       int64_t p10;
       pow10_i64(lit.scale, p10);
       int64_t u = lit.i;
-      int64_t fl = u >= 0 ? u / p10 : -((-u + p10 - 1) / p10);  // floor
+      int64_t fl = floor_div(u, p10);
       bool integral = (u % p10) == 0;
       int64_t ce = integral ? fl : fl + 1;                      // ceil
       p.ctype = CT_INT;

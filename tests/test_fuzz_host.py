@@ -157,7 +157,8 @@ def test_arrow_import_fuzz(L, fmt, n, off, null_count, present, nbuf):
 _COLS = [("a", "f64"), ("b", "i64"), ("c", "i32"), ("s", "utf8")]
 _NUM = ["a", "b", "c", "`a`", "`b`", "`c`"]
 _LITS = ["0", "1", "-3", "2.5", "-0.0", "1e3", "1.0e-2", "9223372036854775807", "-9223372036854775808",
-         "0.000000000000000000001", "NULL"]
+         "0.000000000000000000001", "NULL", "16777217.", "9007199254740993", "9.007199254740993e15",
+         "922337203685477580.7", "-922337203685477580.7"]
 _OPS = [">", ">=", "<", "<=", "=", "==", "!=", "<>"]
 
 
@@ -168,7 +169,7 @@ def _atom():
         st.builds(lambda x, o, y: f"{x} {o} {y}", num, st.sampled_from(_OPS), st.one_of(num, lit)),
         st.builds(lambda x, o, y: f"{y} {o} {x}", num, st.sampled_from(_OPS), lit),
         st.builds(lambda x, n: f"{x} IS {n}NULL", num, st.sampled_from(["", "NOT "])),
-        st.builds(lambda x, d, o, y: f"COALESCE({x}, {d}) {o} {y}", num, st.sampled_from(["0", "1.5", "-2"]),
+        st.builds(lambda x, d, o, y: f"COALESCE({x}, {d}) {o} {y}", num, st.sampled_from(["0", "1.5", "-2", "1e0"]),
                   st.sampled_from(_OPS), lit),
         st.sampled_from(["TRUE", "FALSE", "NULL", "1 < 2", "s = 'x'", "s IN ('a', 'b')", "s IS NULL"]))
 

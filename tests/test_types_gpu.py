@@ -143,7 +143,7 @@ PREDICATES = [
     "COALESCE(c_i16, 0.0) >= 0", "c_i8 = 5", "c_i8 != 0", "COALESCE(c_i8, 1.0) > 0", "c_i8 < c_i16",
     "c_f32 < c_i16", "c_f32 >= c_i8", "c_bool", "NOT c_bool", "c_bool = false", "c_bool != true", "c_bool > false",
     "c_bool IS NULL", "c_date32 IS NOT NULL", "c_timestamp IS NULL", "c_bool OR c_i8 > 100",
-    "(c_f32 > 0 AND c_bool) OR c_i16 IS NULL",
+    "(c_f32 > 0 AND c_bool) OR c_i16 IS NULL", "c_f32 = 16777217.", "COALESCE(c_f32, 0.5) >= 16777217",
 ]
 
 
@@ -311,6 +311,7 @@ def test_quantiles_new_types_vs_oracle(dq, n, dtype):
 NARROW_PREDICATES = [
     "c_f32 > 3", "c_f32 >= 16777217", "COALESCE(c_f32, 0.0) >= 0", "c_f32 < c_i16", "c_i16 > 2.5",
     "COALESCE(c_i16, 1.0) > 0", "c_i8 = 5", "c_i8 < c_i16", "c_i8 IS NULL OR c_f32 > 1e2", "NOT (c_i8 > 0)",
+    "c_f32 = 16777217.", "COALESCE(c_f32, 0.5) >= 16777217",
 ]
 
 
