@@ -306,9 +306,14 @@ __device__ __forceinline__ void block_masks(const uint32_t* validity, const uint
 // count is a popcount of the masks (scalar), so no lane keeps a count, and nothing is merged inside the loop;
 // at the range's end the wave's sums give (n, mean = shift + S1 / n, m2 = S2 - S1^2 / n), which merge across
 // waves / ranges / chunks with StandardDeviationState.sum's algebra (Chan, StandardDeviation.scala:37-44).
-// Accuracy: the range's first group is part of the range, so n (shift - mean)^2 <= (rows / 64) m2 for any
-// data and the cancellation in m2 costs at most ~1e-13 relative at 2^16-row ranges (the Correlation pass
-// uses the same shifts: tests/test_pair_lane.py drift test; full-scale C2 / C5 in tests/fullscale_parity.py).
+// Accuracy: the shift group's k finite selected values are part of the range, so (shift - mean)^2 <= m2 / k
+// and n (shift - mean)^2 <= (n / k) m2 for any data (n: the range's selected rows): the cancellation in m2
+// costs ~(n / k) ulp.  k is not the group's 64 rows: under a sparse validity bitmap or `where` it can be 1, and
+// one far value alone in a range's first group then cost 2e-11 of m2 at 20 K-row ranges.  So the shift group is
+// the first one with at least kShiftMinRows selected rows (shift_group_start), and only a range without such
+// a group takes its first group with any (tests/test_moments_adversarial.py: measured errors in DESIGN.md
+// section 2; the Correlation pass uses the same shifts: tests/test_pair_lane.py drift test; full-scale C2 / C5
+// in tests/fullscale_parity.py).
 struct LaneMoments {
   double sd, sdd;
   int64_t is;  // wrapping int64 sum (integral kinds; Spark Sum on LongType)
@@ -342,12 +347,42 @@ __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
   return v;
 }
 
-// the range's shift: mean of its first 64-row group with finite selected values (0 if none); groups with no
-// selected row are skipped on their bitmap words alone
+// selected rows a 64-row group needs to give its range's shift while the range has such a group
+constexpr int kShiftMinRows = 32;
+
+// the first 64-row group of [row0, row1) with at least kShiftMinRows selected rows (row0 if there is none),
+// from the bitmap words alone: lane l counts group l of each 4096-row stretch (row0 % 64 == 0; the words read
+// are those the range's own pass reads).  Wave-uniform.
+__device__ int64_t shift_group_start(const uint32_t* validity, const uint32_t* mask, int64_t row0, int64_t row1,
+                                     int lane) {
+  if (!validity && !mask) return row0;
+  for (int64_t base = row0; base < row1; base += 64 * 64) {
+    const int64_t r = base + 64 * lane;
+    int c = 0;
+    if (r < row1) {
+      const int64_t w = r >> 5;
+      const bool two = r + 32 < row1;
+      uint64_t sel = ~0ull;
+      if (validity) sel = ((uint64_t)(two ? validity[w + 1] : 0u) << 32) | validity[w];
+      if (mask) sel &= ((uint64_t)(two ? mask[w + 1] : 0u) << 32) | mask[w];
+      if (r + 64 > row1) sel &= (1ull << (row1 - r)) - 1ull;
+      c = __builtin_popcountll(sel);
+    }
+    const uint64_t ok = __builtin_amdgcn_ballot_w64(c >= kShiftMinRows);
+    if (ok != 0) return base + 64 * (int64_t)__builtin_amdgcn_readfirstlane(__builtin_ctzll(ok));
+  }
+  return row0;
+}
+
+// the range's shift: mean of the finite selected values of one 64-row group (0 if the range has none) -- the
+// first group from shift_group_start on that holds any, else the first one before it; groups with no selected
+// row are skipped on their bitmap words alone
 template <int KIND>
 __device__ double range_shift_of(__amdgpu_buffer_rsrc_t vr, const uint32_t* validity, const uint32_t* mask, int64_t row0,
                                  int64_t row1, int lane) {
-  for (int64_t r = row0; r < row1; r += 64) {
+  const int64_t groups = (row1 - row0 + 63) >> 6, g0 = (shift_group_start(validity, mask, row0, row1, lane) - row0) >> 6;
+  for (int64_t i = 0; i < groups; ++i) {
+    const int64_t r = row0 + 64 * (g0 + i < groups ? g0 + i : g0 + i - groups);  // groups g0 .., then 0 .. g0 - 1
     uint64_t sel = ~0ull;
     {
       const int64_t w = r >> 5;
@@ -1248,10 +1283,13 @@ __device__ void decimal_range(const void* values, const uint32_t* validity, cons
       hi = __builtin_nontemporal_load(v + 2 * r + 1);
     }
   };
-  // the range's shift: mean of the casts of its first 64-row group with a selected value
+  // the range's shift: mean of the casts of the selected values of one 64-row group, chosen as range_shift_of
+  // does (the first group with kShiftMinRows selected rows, else the first with any)
   double shift = 0.0;
   if (STATS) {
-    for (int64_t r = row0; r < row1; r += 64) {
+    const int64_t groups = (row1 - row0 + 63) >> 6, g0 = (shift_group_start(validity, mask, row0, row1, lane) - row0) >> 6;
+    for (int64_t i = 0; i < groups; ++i) {
+      const int64_t r = row0 + 64 * (g0 + i < groups ? g0 + i : g0 + i - groups);
       uint64_t sel = ~0ull;
       const int64_t w = r >> 5;
       const bool two = r + 32 < row1;

@@ -27,11 +27,15 @@
 // the checked fold: selections cut to finite rows, Spark's poisoning of the pairs holding a NaN / inf in
 // a row selected in both columns, NaN / +-inf counts and min / max over the inf rows for the moments.
 //
-// Shifts.  Per (range, position): the mean of the column's first 64-row group holding finite selected
-// values.  That makes the closing formulas m2 = Saa - Sa^2 / n and ck = Sab - Sa Sb / n safe:
-// |shift - mean|^2 <= (rows / 64) var for any data, so the cancellation costs at most ~1e-13 relative at
-// 2^16-row ranges (tests/test_pair_lane.py::test_pair_pass_drift_and_offset_columns against a
-// double-double reference; the full-scale C4 check in tests/fullscale_parity.py).  Each pair and each
+// Shifts.  Per (range, position): the mean of the finite selected values of one 64-row group of the column:
+// the first group with at least kShiftMinRows selected rows, else the first with any (range_shift).  That
+// makes the closing formulas m2 = Saa - Sa^2 / n and ck = Sab - Sa Sb / n safe: with k finite selected
+// values in the shift group, |shift - mean|^2 <= (n / k) var for any data (n: the range's selected rows), so
+// the cancellation costs ~(n / k) ulp.  k is the group's selected values, not its 64 rows: one far value
+// alone in a range's first group (k = 1) cost 4e-11 of m2 and 2e-11 of the correlation at 20 K-row ranges
+// before the kShiftMinRows rule (tests/test_moments_adversarial.py, figures in DESIGN.md section 2;
+// tests/test_pair_lane.py::test_pair_pass_drift_and_offset_columns against a double-double reference; the
+// full-scale C4 check in tests/fullscale_parity.py).  Each pair and each
 // moments column belongs to exactly one wave: at the end of the range the wave reduces its lanes (fixed
 // butterfly order) and writes its CorrPartial / ColPartial records; dq_finalize merges the ranges in order.
 #include <hip/hip_runtime.h>
@@ -130,10 +134,29 @@ __device__ __forceinline__ double raw_to_double(int64_t raw, int kind) {
 }
 __device__ __forceinline__ int elem_bytes(int kind) { return ck_bytes(kind & 0xFF); }
 
-// the shift of a column in a range (pointers at the range's first row, nr rows): the mean of its first 64-row group holding finite selected values
+// selected rows a 64-row group needs to give its range's shift while the range has such a group
+constexpr int kShiftMinRows = 32;
+
+// the shift of a column in a range (pointers at the range's first row, nr rows): the mean of the finite selected
+// values of one 64-row group -- the first group with at least kShiftMinRows selected rows (found on the bitmap
+// words alone: lane l counts group l of each 4096-row stretch) or any after it that holds a finite selected
+// value, else the first such group before it
 __device__ double range_shift(const char* col, int kind, const uint32_t* vb, const uint32_t* where, int64_t nr,
                               int lane) {
-  for (int64_t gr = 0; gr < nr; gr += 64) {
+  const int64_t groups = (nr + 63) >> 6;
+  int64_t g0 = 0;
+  for (int64_t base = 0; base < nr; base += 64 * 64) {
+    const int64_t gr = base + 64 * lane;
+    int c = 0;
+    if (gr < nr) c = __builtin_popcountll(vbits64_tail(vb, gr, nr) & vbits64_tail(where, gr, nr));
+    const uint64_t ok = __builtin_amdgcn_ballot_w64(c >= kShiftMinRows);
+    if (ok != 0) {
+      g0 = (base >> 6) + __builtin_amdgcn_readfirstlane(__builtin_ctzll(ok));
+      break;
+    }
+  }
+  for (int64_t i = 0; i < groups; ++i) {
+    const int64_t gr = 64 * (g0 + i < groups ? g0 + i : g0 + i - groups);
     const int64_t r = gr + lane < nr ? gr + lane : nr - 1;
     const double x = raw_to_double(load_raw(col, kind, r), kind);
     const uint64_t fm = __builtin_amdgcn_ballot_w64(__builtin_isfinite(x)) & bits64_tail(vb, gr, nr) &

@@ -2153,6 +2153,11 @@ dq_status dq_finish(dq_plan* p, dq_state* out) {
         break;
       case DQ_OP_STDDEV:
         s.u.stddev.n = c->n; s.u.stddev.avg = c->mean; s.u.stddev.m2 = c->m2;
+        // Spark's final aggregate merges its first partial into the zero buffer (CentralMomentAgg's merge, the
+        // algebra of StandardDeviation.scala:37-44): m2 + delta * deltaN * n1 * n2 with n1 = 0, delta = avg.
+        // The term is +-0 unless avg * (avg / n) overflows: then inf * 0 makes Spark's m2 NaN, where the
+        // overflowing squares alone leave +inf (tests/test_moments_adversarial.py, `wide`)
+        if (c->n > 0.0) s.u.stddev.m2 += c->mean * (c->mean / c->n) * 0.0 * c->n;
         if (c->pinf_count + c->ninf_count > 0) {
           // an infinite value makes Spark's m2 NaN (delta * (x - avg) = inf * (inf - inf)) and its avg
           // inf or NaN depending on the row order; the metric sqrt(m2 / n) is NaN either way
