@@ -22,6 +22,7 @@
 #include "dq_hash.h"
 #include "dq_decimal.h"
 #include "dq_lane.h"
+#include "dq_shift.h"
 
 namespace dq {
 
@@ -285,16 +286,7 @@ __device__ __forceinline__ void block_masks(const uint32_t* validity, const uint
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int32_t left = rem - 64 * j;  // rows of group j below row1
-    const int64_t w = w0 + 2 * j;
-    uint64_t x = 0;
-    if (left > 0) {
-      const bool two = left > 32;  // the second dword holds rows below row1
-      x = ~0ull;
-      if (validity) x = ((uint64_t)(two ? ((const_u32s)validity)[w + 1] : 0u) << 32) | ((const_u32s)validity)[w];
-      if (mask) x &= ((uint64_t)(two ? ((const_u32s)mask)[w + 1] : 0u) << 32) | ((const_u32s)mask)[w];
-      if (left < 64) x &= (1ull << left) - 1ull;
-    }
-    m[j] = x;
+    m[j] = left > 0 ? sel_word(validity, mask, w0 + 2 * j, left) : 0;
   }
 }
 
@@ -302,18 +294,11 @@ __device__ __forceinline__ void block_masks(const uint32_t* validity, const uint
 // Moments of a numeric column (lane l of a wave owns rows base + 64 j + l) as shifted sums over the whole
 // workgroup range: sd = sum(x - shift), sdd = sum((x - shift)^2) per lane under the selection mask --
 // exec-masked updates, so an unselected row costs no VALU work -- with ONE shift for the range (wave-uniform,
-// in SGPRs): the mean of the range's first 64-row group holding finite selected values.  The selected-row
+// in SGPRs): the mean of the finite selected values of one 64-row group (which group, and what that costs in m2:
+// range_shift, dq_shift.h).  The selected-row
 // count is a popcount of the masks (scalar), so no lane keeps a count, and nothing is merged inside the loop;
 // at the range's end the wave's sums give (n, mean = shift + S1 / n, m2 = S2 - S1^2 / n), which merge across
 // waves / ranges / chunks with StandardDeviationState.sum's algebra (Chan, StandardDeviation.scala:37-44).
-// Accuracy: the shift group's k finite selected values are part of the range, so (shift - mean)^2 <= m2 / k
-// and n (shift - mean)^2 <= (n / k) m2 for any data (n: the range's selected rows): the cancellation in m2
-// costs ~(n / k) ulp.  k is not the group's 64 rows: under a sparse validity bitmap or `where` it can be 1, and
-// one far value alone in a range's first group then cost 2e-11 of m2 at 20 K-row ranges.  So the shift group is
-// the first one with at least kShiftMinRows selected rows (shift_group_start), and only a range without such
-// a group takes its first group with any (tests/test_moments_adversarial.py: measured errors in DESIGN.md
-// section 2; the Correlation pass uses the same shifts: tests/test_pair_lane.py drift test; full-scale C2 / C5
-// in tests/fullscale_parity.py).
 struct LaneMoments {
   double sd, sdd;
   int64_t is;  // wrapping int64 sum (integral kinds; Spark Sum on LongType)
@@ -330,73 +315,6 @@ __device__ __forceinline__ double range_value(__amdgpu_buffer_rsrc_t vr, int64_t
   const auto w2 = __builtin_amdgcn_raw_buffer_load_b64(vr, (int)(rel * 8), 0, 0);
   if constexpr (KIND == CK_F64) return __builtin_bit_cast(double, ((uint64_t)w2[1] << 32) | w2[0]);
   return __builtin_fma((double)(int32_t)w2[1], 4294967296.0, (double)w2[0]);
-}
-__device__ __forceinline__ double wave_uniform(double v) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = (int64_t)((uint64_t)v + (uint64_t)__shfl_xor(v, m));
-  return v;
-}
-
-// selected rows a 64-row group needs to give its range's shift while the range has such a group
-constexpr int kShiftMinRows = 32;
-
-// the first 64-row group of [row0, row1) with at least kShiftMinRows selected rows (row0 if there is none),
-// from the bitmap words alone: lane l counts group l of each 4096-row stretch (row0 % 64 == 0; the words read
-// are those the range's own pass reads).  Wave-uniform.
-__device__ int64_t shift_group_start(const uint32_t* validity, const uint32_t* mask, int64_t row0, int64_t row1,
-                                     int lane) {
-  if (!validity && !mask) return row0;
-  for (int64_t base = row0; base < row1; base += 64 * 64) {
-    const int64_t r = base + 64 * lane;
-    int c = 0;
-    if (r < row1) {
-      const int64_t w = r >> 5;
-      const bool two = r + 32 < row1;
-      uint64_t sel = ~0ull;
-      if (validity) sel = ((uint64_t)(two ? validity[w + 1] : 0u) << 32) | validity[w];
-      if (mask) sel &= ((uint64_t)(two ? mask[w + 1] : 0u) << 32) | mask[w];
-      if (r + 64 > row1) sel &= (1ull << (row1 - r)) - 1ull;
-      c = __builtin_popcountll(sel);
-    }
-    const uint64_t ok = __builtin_amdgcn_ballot_w64(c >= kShiftMinRows);
-    if (ok != 0) return base + 64 * (int64_t)__builtin_amdgcn_readfirstlane(__builtin_ctzll(ok));
-  }
-  return row0;
-}
-
-// the range's shift: mean of the finite selected values of one 64-row group (0 if the range has none) -- the
-// first group from shift_group_start on that holds any, else the first one before it; groups with no selected
-// row are skipped on their bitmap words alone
-template <int KIND>
-__device__ double range_shift_of(__amdgpu_buffer_rsrc_t vr, const uint32_t* validity, const uint32_t* mask, int64_t row0,
-                                 int64_t row1, int lane) {
-  const int64_t groups = (row1 - row0 + 63) >> 6, g0 = (shift_group_start(validity, mask, row0, row1, lane) - row0) >> 6;
-  for (int64_t i = 0; i < groups; ++i) {
-    const int64_t r = row0 + 64 * (g0 + i < groups ? g0 + i : g0 + i - groups);  // groups g0 .., then 0 .. g0 - 1
-    uint64_t sel = ~0ull;
-    {
-      const int64_t w = r >> 5;
-      const bool two = r + 32 < row1;
-      if (validity) sel = ((uint64_t)(two ? ((const_u32s)validity)[w + 1] : 0u) << 32) | ((const_u32s)validity)[w];
-      if (mask) sel &= ((uint64_t)(two ? ((const_u32s)mask)[w + 1] : 0u) << 32) | ((const_u32s)mask)[w];
-      if (r + 64 > row1) sel &= (1ull << (row1 - r)) - 1ull;
-    }
-    if (sel == 0) continue;
-    const double x = range_value<KIND>(vr, r - row0 + lane);
-    const uint64_t fm = __builtin_amdgcn_ballot_w64(__builtin_isfinite(x)) & sel;
-    if (fm != 0) return wave_uniform(wave_sum_f64(lane_bit(fm) ? x : 0.0) / (double)__builtin_popcountll(fm));
-  }
-  return 0.0;
 }
 
 // Exec-masked moment / min / max update of one value (inline asm so the accumulators are plain
@@ -498,15 +416,7 @@ __device__ __forceinline__ void float_block_checked(__amdgpu_buffer_rsrc_t vr, c
   for (int j = 0; j < 8; ++j) {
     const int32_t left = rem - 64 * j;
     if (left <= 0) break;
-    const int64_t r = base + 64 * j;
-    uint64_t mj = ~0ull;
-    {
-      const int64_t w = r >> 5;
-      const bool two = left > 32;
-      if (validity) mj = ((uint64_t)(two ? ((const_u32s)validity)[w + 1] : 0u) << 32) | ((const_u32s)validity)[w];
-      if (mask) mj &= ((uint64_t)(two ? ((const_u32s)mask)[w + 1] : 0u) << 32) | ((const_u32s)mask)[w];
-      if (left < 64) mj &= (1ull << left) - 1ull;
-    }
+    const uint64_t mj = sel_word(validity, mask, (base + 64 * j) >> 5, left);
     uint64_t b;
     double xv;
     if constexpr (kF32) {
@@ -579,7 +489,8 @@ __device__ void numeric_range(const void* values, const uint32_t* validity, cons
   int64_t nan_v = 0, pinf_v = 0, ninf_v = 0;
   int64_t cnt_w = 0;  // wave-uniform count of the rows in the moments (STATS) / selected rows (HLL only)
   LaneMoments a{0.0, 0.0, 0};
-  const double shift = STATS ? range_shift_of<KIND>(vr, validity, mask, row0, row1, lane) : 0.0;
+  const double shift =
+      STATS ? range_shift(validity, mask, row0, row1, lane, [=](int64_t r) { return range_value<KIND>(vr, r - row0); }) : 0.0;
   int32_t qmin = 0;
   const int32_t nr = (int32_t)(row1 - row0);  // range-relative rows: 32-bit (scalar) loop control and compares
   for (int32_t rb = 0; rb < nr; rb += kRowsPerIter) {
@@ -1276,34 +1187,19 @@ __device__ void decimal_range(const void* values, const uint32_t* validity, cons
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t* v = reinterpret_cast<const uint64_t*>(values);
-  auto load = [&](int64_t r, uint64_t& lo, uint64_t& hi) {
+  auto load = [=](int64_t r, uint64_t& lo, uint64_t& hi) {
     lo = hi = 0;
     if (r < row1) {
       lo = __builtin_nontemporal_load(v + 2 * r);
       hi = __builtin_nontemporal_load(v + 2 * r + 1);
     }
   };
-  // the range's shift: mean of the casts of the selected values of one 64-row group, chosen as range_shift_of
-  // does (the first group with kShiftMinRows selected rows, else the first with any)
-  double shift = 0.0;
-  if (STATS) {
-    const int64_t groups = (row1 - row0 + 63) >> 6, g0 = (shift_group_start(validity, mask, row0, row1, lane) - row0) >> 6;
-    for (int64_t i = 0; i < groups; ++i) {
-      const int64_t r = row0 + 64 * (g0 + i < groups ? g0 + i : g0 + i - groups);
-      uint64_t sel = ~0ull;
-      const int64_t w = r >> 5;
-      const bool two = r + 32 < row1;
-      if (validity) sel = ((uint64_t)(two ? ((const_u32s)validity)[w + 1] : 0u) << 32) | ((const_u32s)validity)[w];
-      if (mask) sel &= ((uint64_t)(two ? ((const_u32s)mask)[w + 1] : 0u) << 32) | ((const_u32s)mask)[w];
-      if (r + 64 > row1) sel &= (1ull << (row1 - r)) - 1ull;
-      if (sel == 0) continue;
-      uint64_t lo, hi;
-      load(r + lane, lo, hi);
-      const double x = lane_bit(sel) ? dec_to_double(lo, hi, sc, tab, prec <= 18) : 0.0;
-      shift = wave_uniform(wave_sum_f64(x) / (double)__builtin_popcountll(sel));
-      break;
-    }
-  }
+  // the range's shift from the casts (always finite; rows past row1 read as 0)
+  const double shift = !STATS ? 0.0 : range_shift(validity, mask, row0, row1, lane, [=](int64_t r) {
+    uint64_t lo, hi;
+    load(r, lo, hi);
+    return dec_to_double(lo, hi, sc, tab, prec <= 18);
+  });
   LaneMoments a{0.0, 0.0, 0};
   uint64_t slo = 0, shi = 0;  // the lane's exact sum (128-bit, wrapping)
   double guard = 0.0;

@@ -27,15 +27,8 @@
 // the checked fold: selections cut to finite rows, Spark's poisoning of the pairs holding a NaN / inf in
 // a row selected in both columns, NaN / +-inf counts and min / max over the inf rows for the moments.
 //
-// Shifts.  Per (range, position): the mean of the finite selected values of one 64-row group of the column:
-// the first group with at least kShiftMinRows selected rows, else the first with any (range_shift).  That
-// makes the closing formulas m2 = Saa - Sa^2 / n and ck = Sab - Sa Sb / n safe: with k finite selected
-// values in the shift group, |shift - mean|^2 <= (n / k) var for any data (n: the range's selected rows), so
-// the cancellation costs ~(n / k) ulp.  k is the group's selected values, not its 64 rows: one far value
-// alone in a range's first group (k = 1) cost 4e-11 of m2 and 2e-11 of the correlation at 20 K-row ranges
-// before the kShiftMinRows rule (tests/test_moments_adversarial.py, figures in DESIGN.md section 2;
-// tests/test_pair_lane.py::test_pair_pass_drift_and_offset_columns against a double-double reference; the
-// full-scale C4 check in tests/fullscale_parity.py).  Each pair and each
+// Shifts.  Per (range, position): the column pass's shift (range_shift, dq_shift.h: the rule and what it costs
+// the closing formulas m2 = Saa - Sa^2 / n and ck = Sab - Sa Sb / n).  Each pair and each
 // moments column belongs to exactly one wave: at the end of the range the wave reduces its lanes (fixed
 // butterfly order) and writes its CorrPartial / ColPartial records; dq_finalize merges the ranges in order.
 #include <hip/hip_runtime.h>
@@ -46,62 +39,16 @@
 #include "dq_decimal.h"
 #include "dq_device.h"
 #include "dq_lane.h"
+#include "dq_shift.h"
 
 namespace dq {
 
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = (int64_t)((uint64_t)v + (uint64_t)__shfl_xor(v, m));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
-  return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = hw_min(v, __shfl_xor(v, m));
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = hw_max(v, __shfl_xor(v, m));
-  return v;
-}
-__device__ __forceinline__ double uniform(double v) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-
 // the 64-bit bitmap word at byte offset `off` (uniform: one scalar load; the bitmap holds it whole)
 __device__ __forceinline__ uint64_t sword_at(const uint32_t* bm, uint32_t off) {
   const const_u32s w = (const_u32s)((const __attribute__((address_space(4))) char*)bm + off);
   return ((uint64_t)w[1] << 32) | w[0];
-}
-// bits of rows [base, base + 64) of a bitmap, clipped to rows below row1 (base < row1, base % 64 == 0; a
-// dword holding no row below row1 is not read).  Uniform base: scalar loads; per-lane base: vector loads.
-__device__ __forceinline__ uint64_t bits64_tail(const uint32_t* bm, int64_t base, int64_t row1) {
-  const int64_t w = base >> 5;
-  const bool two = base + 32 < row1;
-  uint64_t x = ((uint64_t)(two ? ((const_u32s)bm)[w + 1] : 0u) << 32) | ((const_u32s)bm)[w];
-  if (base + 64 > row1) x &= (1ull << (row1 - base)) - 1ull;
-  return x;
-}
-__device__ __forceinline__ uint64_t vbits64_tail(const uint32_t* bm, int64_t base, int64_t row1) {
-  const int64_t w = base >> 5;
-  const bool two = base + 32 < row1;
-  uint64_t x = ((uint64_t)(two ? bm[w + 1] : 0u) << 32) | bm[w];
-  if (base + 64 > row1) x &= (1ull << (row1 - base)) - 1ull;
-  return x;
 }
 
 // DecimalType conversion constants (tools/gen_dec_tables.py)
@@ -133,38 +80,6 @@ __device__ __forceinline__ double raw_to_double(int64_t raw, int kind) {
   return __builtin_fma((double)(int32_t)(raw >> 32), 4294967296.0, (double)(uint32_t)raw);  // exact int64 -> double
 }
 __device__ __forceinline__ int elem_bytes(int kind) { return ck_bytes(kind & 0xFF); }
-
-// selected rows a 64-row group needs to give its range's shift while the range has such a group
-constexpr int kShiftMinRows = 32;
-
-// the shift of a column in a range (pointers at the range's first row, nr rows): the mean of the finite selected
-// values of one 64-row group -- the first group with at least kShiftMinRows selected rows (found on the bitmap
-// words alone: lane l counts group l of each 4096-row stretch) or any after it that holds a finite selected
-// value, else the first such group before it
-__device__ double range_shift(const char* col, int kind, const uint32_t* vb, const uint32_t* where, int64_t nr,
-                              int lane) {
-  const int64_t groups = (nr + 63) >> 6;
-  int64_t g0 = 0;
-  for (int64_t base = 0; base < nr; base += 64 * 64) {
-    const int64_t gr = base + 64 * lane;
-    int c = 0;
-    if (gr < nr) c = __builtin_popcountll(vbits64_tail(vb, gr, nr) & vbits64_tail(where, gr, nr));
-    const uint64_t ok = __builtin_amdgcn_ballot_w64(c >= kShiftMinRows);
-    if (ok != 0) {
-      g0 = (base >> 6) + __builtin_amdgcn_readfirstlane(__builtin_ctzll(ok));
-      break;
-    }
-  }
-  for (int64_t i = 0; i < groups; ++i) {
-    const int64_t gr = 64 * (g0 + i < groups ? g0 + i : g0 + i - groups);
-    const int64_t r = gr + lane < nr ? gr + lane : nr - 1;
-    const double x = raw_to_double(load_raw(col, kind, r), kind);
-    const uint64_t fm = __builtin_amdgcn_ballot_w64(__builtin_isfinite(x)) & bits64_tail(vb, gr, nr) &
-                        bits64_tail(where, gr, nr);
-    if (fm != 0) return wave_sum(lane_bit(fm) ? x : 0.0) / (double)__builtin_popcountll(fm);
-  }
-  return 0.0;
-}
 
 // LDS ring of the fp64 path, per workgroup: kRing slots of two 64-row groups -- the 8 columns (1 KB each) and
 // the 36 selection words (4 per stream: where + 8 columns); 4 slots = 33 KB, 4 workgroups per CU (deeper rings
@@ -405,7 +320,12 @@ __device__ __forceinline__ bool pair_range(const PairWaveTask& T, const ScanCols
     kind[p] = F64 ? CK_F64 : T.kinds[p];
     vw[p] = (cols.validity[c] ? cols.validity[c] : ones) + (row0 >> 5);
     vp[p] = reinterpret_cast<const char*>(cols.values[c]) + row0 * elem_bytes(kind[p]);
-    shift[p] = uniform(range_shift(vp[p], kind[p], vw[p], ww, nr, lane));
+    __builtin_assume(vw[p] != nullptr && ww != nullptr);  // stand-ins, never null: sel_word's null test folds away
+    const char* col = vp[p];
+    const int k = kind[p];
+    shift[p] = range_shift(vw[p], ww, 0, nr, lane, [=](int64_t r) {  // range-local rows; the last row again past it
+      return raw_to_double(load_raw(col, k, r < nr ? r : nr - 1), k);
+    });
   }
   PairAcc A;
 #pragma unroll
@@ -645,6 +565,7 @@ __device__ __forceinline__ bool pair_range(const PairWaveTask& T, const ScanCols
       const int c = tp->cols[p];
       vw[p] = (cols.validity[c] ? cols.validity[c] : ones) + (row0 >> 5);
       vp[p] = reinterpret_cast<const char*>(cols.values[c]) + row0 * 8;
+      __builtin_assume(vw[p] != nullptr);
     }
     // an odd last full group (only at the end of the scan): values and masks loaded directly
     for (int64_t g = 2 * npair; g < nfull; ++g) {
@@ -712,11 +633,11 @@ __device__ __forceinline__ bool pair_range(const PairWaveTask& T, const ScanCols
     const int64_t r = tb + lane < nr ? tb + lane : nr - 1;
     int64_t b[kPairPos];
     uint64_t m[kPairPos];
-    const uint64_t wm = bits64_tail(ww, tb, nr);
+    const uint64_t wm = sel_word(ww, tb >> 5, nr - tb);
 #pragma unroll
     for (int p = 0; p < kPairPos; ++p) {
       b[p] = load_raw(vp[p], kind[p], r);
-      m[p] = bits64_tail(vw[p], tb, nr) & wm;
+      m[p] = sel_word(vw[p], tb >> 5, nr - tb) & wm;
     }
     fold<CHECKED, F64, MINMAX>(A, b, m, shift, kind);
   }
@@ -741,10 +662,10 @@ __device__ __forceinline__ bool pair_range(const PairWaveTask& T, const ScanCols
 #pragma unroll
   for (int k = 0; k < kPairMoments; ++k) mc[k] = 0;
   for (int64_t base = 64 * lane; base < nr; base += 64 * 64) {
-    const uint64_t wm = vbits64_tail(ww, base, nr);
+    const uint64_t wm = sel_word<true>(ww, base >> 5, nr - base);
     uint64_t w[kPairPos];
 #pragma unroll
-    for (int p = 0; p < kPairPos; ++p) w[p] = vbits64_tail(vw[p], base, nr) & wm;
+    for (int p = 0; p < kPairPos; ++p) w[p] = sel_word<true>(vw[p], base >> 5, nr - base) & wm;
 #pragma unroll
     for (int q = 0; q < kPairSlots; ++q) pc[q] += (uint32_t)__builtin_popcountll(w[kPairSlotA[q]] & w[kPairSlotB[q]]);
 #pragma unroll
@@ -757,7 +678,7 @@ __device__ __forceinline__ bool pair_range(const PairWaveTask& T, const ScanCols
     if (!((T.pair_mask >> q) & 1u)) continue;
     double S[5];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) S[k] = wave_sum(A.s[q][k]);
+    for (int k = 0; k < 5; ++k) S[k] = wave_sum_f64(A.s[q][k]);
     const uint32_t cnt = wave_sum_u32(pc[q]);
     if (lane == 0) {
       CorrPartial* o = pair_part + (size_t)T.pair_out[q] * kMaxWG + range;
@@ -784,7 +705,7 @@ __device__ __forceinline__ bool pair_range(const PairWaveTask& T, const ScanCols
 #pragma unroll
   for (int k = 0; k < kPairMoments; ++k) {
     if (!((T.mom_mask >> k) & 1u)) continue;
-    const double S1 = wave_sum(A.sd[k]), S2 = wave_sum(A.sdd[k]);
+    const double S1 = wave_sum_f64(A.sd[k]), S2 = wave_sum_f64(A.sdd[k]);
     const double fmin = wave_min(A.lo[k]), fmax = wave_max(A.hi[k]);
     const int64_t isum = wave_sum_i64(A.is[k]);
     const int64_t count = wave_sum_u32(mc[k]);
