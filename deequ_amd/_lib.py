@@ -238,6 +238,9 @@ def _load():
     L.dq_quantile_digest.restype = c.c_int32
     L.dq_quantile_digest.argtypes = [c.c_int32, P(ColumnView), P(c.c_int64), c.c_int32, c.c_double, c.c_int32,
                                      c.c_void_p, P(c.c_double), P(c.c_int64), c.c_int64, P(c.c_int64), P(c.c_int64)]
+    L.dq_cast_utf8.restype = c.c_int32
+    L.dq_cast_utf8.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_int32, c.c_void_p, c.c_void_p, c.c_int32,
+                               c.c_void_p, P(c.c_int64)]
     L.dq_freq_top.restype = c.c_int32
     L.dq_freq_top.argtypes = [c.c_void_p, c.c_int32, P(c.c_uint64), P(c.c_int64), P(c.c_uint64), P(c.c_int32)]
     L.dq_freq_destroy.restype = None
@@ -308,7 +311,7 @@ EXPORTED = [
     "dq_plan_enable_timing", "dq_plan_kernel_time", "dq_plan_variant_bytes_per_row_x1000",
     "dq_plan_kernel_bytes_per_row_x1000", "dq_plan_pred_compiled", "dq_plan_pred_wait",
     "dq_state_merge", "dq_state_combine", "dq_state_merge_n", "dq_state_combine_n", "dq_state_is_defined", "dq_state_metric", "dq_hll_estimate",
-    "dq_state_to_bytes", "dq_state_from_bytes", "dq_state_identifier",
+    "dq_state_to_bytes", "dq_state_from_bytes", "dq_state_identifier", "dq_cast_utf8",
 ]
 
 

@@ -438,6 +438,23 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
 dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows, int32_t n_chunks,
                              double relative_error, int32_t device, void* hip_stream, double* values, int64_t* ranks,
                              int64_t cap, int64_t* n_samples, int64_t* count);
+/* Cast(StringType -> LongType | DoubleType), Spark 2.2: the ColumnProfiler's castNumericStringColumns
+ * (profiles/ColumnProfiler.scala:133-141, 330-339, 399-417), materialised as withColumn(... cast ...) does so that
+ * every analyzer above reads the result as an ordinary I64 / F64 column.  to_type: DQ_TYPE_I64 or DQ_TYPE_F64.
+ * src: a DQ_TYPE_UTF8 / DQ_TYPE_LARGE_UTF8 view of n_rows.  out_values: 8 * n_rows bytes (16-byte aligned),
+ * out_validity: 8 * ceil(n_rows / 64) bytes (8-byte aligned; bits past n_rows are written 0); both device,
+ * caller-allocated.  Row r of the result is NULL (value 0) iff the source row is NULL or the cast fails;
+ * *null_count (host, optional) = NULL rows of the result.
+ * To long (UTF8String.toLong, raw bytes, no trimming): [+-]digits[.digits], the fraction dropped, Java's overflow
+ * checks (-9223372036854775808 is a value, 9223372036854775808 NULL); "", a lone sign and any other byte are NULL.
+ * To double (java.lang.Double.parseDouble): blanks (<= U+0020) trimmed, [+-] then NaN | Infinity | a decimal with
+ * optional exponent | a Java hex float, the last two with an optional fFdD suffix; correctly rounded (nearest
+ * even), overflow to +-Infinity, underflow through subnormals to +-0; everything else NULL.  Values outside the
+ * device's exact fast tier (more than 38 significant digits, large exponents, hex floats) are converted on the host
+ * and patched in before the call returns: every row is exact.  Synchronises hip_stream. */
+dq_status dq_cast_utf8(int32_t src_type, const dq_column_view* src, int64_t n_rows, int32_t to_type,
+                       void* out_values, uint8_t* out_validity, int32_t device, void* hip_stream,
+                       int64_t* null_count);
 /* Histogram (analyzers/Histogram.scala:33-99): the n largest groups by count (ties in key order):
  * key, count and -- for a table built from data with hashed keys (strings) -- one representative row
  * id (chunk << 40 | row) whose value the caller renders; ~0 when not available (merged tables). */
