@@ -129,10 +129,36 @@ struct HllKey {
   uint32_t addr;
   int32_t q;
 };
-__device__ __forceinline__ HllKey hll_key_from_fmix(uint64_t b) {
+__device__ __forceinline__ uint32_t hll_hi_from_fmix(uint64_t b) {
   const uint32_t bl = (uint32_t)b, bh = (uint32_t)(b >> 32);
-  const uint32_t hi = __umulhi(bl, (uint32_t)XP3) + bl * (uint32_t)(XP3 >> 32) + bh * (uint32_t)XP3;
+  return __umulhi(bl, (uint32_t)XP3) + bl * (uint32_t)(XP3 >> 32) + bh * (uint32_t)XP3;
+}
+__device__ __forceinline__ HllKey hll_key_from_fmix(uint64_t b) {
+  const uint32_t hi = hll_hi_from_fmix(b);
   return {(hi >> 21) & 0x7FCu, ffbh_raw(hi << 9)};
+}
+
+// The floor test (DESIGN §2 "HLL floor").  dq_finalize leaves, per HLL slot, the minimum over the 512 registers
+// of the plan's accumulator (encoding 0 = empty, q + 1 otherwise) as it stood after the previous chunk.  A
+// value whose q + 1 is <= that minimum can raise neither its workgroup register's contribution nor the
+// accumulator (registers only grow, the result is a max), so it needs no register update at all.  With
+// qfloor = floor - 1 the values that still matter are those with q > qfloor, i.e. rank word (hi << 9) below
+// thr = 2^(31 - qfloor); qfloor is clamped at 22 so that thr >= 2^9 keeps hi << 9 == 0 (the rank needs the hash's
+// low word, q >= 23) inside the test.  A block of 512 rows folds its rank words with min and takes one ballot;
+// a block in which any lane passes is redone exactly.
+//
+// kFloorMin, the smallest qfloor at which the test replaces the per-value update: a 512-row block of a numeric
+// pass is redone with probability 1 - (1 - 2^-(qfloor + 1))^512 -- 11.8 % at 11, 6.1 % at 12, 3.1 % at 13, 0.8 %
+// at 15 -- and a redo costs about one block (~42 VALU per value), i.e. ~5 / 2.6 / 1.3 / 0.3 VALU per value against
+// the ~3.7 VALU and 0.75 LDS instructions per value the test was measured to save at floors near 15.  By that
+// arithmetic 12 is about even and 13 clearly ahead; the region 12..14 itself has not been measured (the
+// benchmark's floors sit at 15-16), so the constant is the conservative 13.  (The string pass does not use the floor: the
+// variant that did was measured and dropped)
+constexpr int32_t kFloorMin = 13;
+__device__ __forceinline__ uint32_t hll_floor_thr(const uint32_t* __restrict__ hll_floor, int32_t slot) {
+  if (!hll_floor || slot < 0) return 0u;
+  const int32_t qfloor = (int32_t)hll_floor[slot] - 1;
+  return qfloor >= kFloorMin ? 1u << (31 - min(qfloor, 22)) : 0u;
 }
 // XXH64.hashLong / hashInt (seed 42) -> HLL key (StatefulHyperloglogPlus.scala:93 via XxHash64Function)
 __device__ __forceinline__ HllKey hll_key_long(uint64_t v) { return hll_key_from_fmix(xxh64_long_head(v)); }
@@ -372,22 +398,32 @@ __device__ __forceinline__ void masked_moments(LaneMoments& a, double& lo, doubl
 // One 512-row block of a wave: x[j] the lane's value of row group j as a double, bits[j] its raw 64-bit
 // pattern (i32 / i16 / i8: sign-extended; f32: its 32 bits), m[j] the selection masks (every selected value finite: a block with a
 // selected NaN / +-inf takes the caller's rolled path).
-template <int KIND, bool STATS, bool HLL>
+// FLOOR: the floor test instead of the per-value register update (thr from hll_floor_thr, non-zero); rows outside
+// the selection join the min -- they can only trigger the redo, which applies selected rows alone.
+template <int KIND, bool STATS, bool HLL, bool FLOOR = false>
 __device__ __forceinline__ void numeric_block(const double (&x)[8], const uint64_t (&bits)[8], const uint64_t (&m)[8],
-                                              double shift, ColStats& s, LaneMoments& a, int32_t* regs, int32_t& qmin) {
+                                              double shift, ColStats& s, LaneMoments& a, int32_t* regs, int32_t& qmin,
+                                              uint32_t thr = 0) {
+  uint32_t rmin = ~0u;  // FLOOR: min of the block's rank words hi << 9
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     if (STATS) masked_moments<!ck_float(KIND), false>(a, s.fmin, s.fmax, x[j], bits[j], shift, m[j], m[j]);
     if (HLL) {
-      const HllKey key = ck_bytes(KIND) <= 4 ? hll_key_int((uint32_t)bits[j]) : hll_key_long(bits[j]);
-      qmin = min(qmin, key.q);
-      if (lane_bit(m[j])) atomicMax(reinterpret_cast<int32_t*>(reinterpret_cast<char*>(regs) + key.addr), key.q);
+      if constexpr (FLOOR) {
+        const uint64_t b = ck_bytes(KIND) <= 4 ? xxh64_int_head((uint32_t)bits[j]) : xxh64_long_head(bits[j]);
+        rmin = min(rmin, hll_hi_from_fmix(b) << 9);
+      } else {
+        const HllKey key = ck_bytes(KIND) <= 4 ? hll_key_int((uint32_t)bits[j]) : hll_key_long(bits[j]);
+        qmin = min(qmin, key.q);
+        if (lane_bit(m[j])) atomicMax(reinterpret_cast<int32_t*>(reinterpret_cast<char*>(regs) + key.addr), key.q);
+      }
     }
   }
   if (HLL) {
-    // rare (2^-23 per value): a rank that needs the hash's low word -- redo the block's selected
-    // values exactly (register max is idempotent)
-    if (__builtin_amdgcn_ballot_w64(qmin < 0) != 0) {
+    // rare: a rank that needs the hash's low word (2^-23 per value), or FLOOR: a value above the floor
+    // (2^-(qfloor + 1) per value) -- redo the block's selected values exactly (register max is idempotent)
+    const bool redo = FLOOR ? rmin < thr : qmin < 0;
+    if (__builtin_amdgcn_ballot_w64(redo) != 0) {
 #pragma unroll 1
       for (int j = 0; j < 8; ++j) {
         if (lane_bit(m[j])) hll_update(regs, ck_bytes(KIND) <= 4 ? xxh64_int((uint32_t)bits[j]) : xxh64_long(bits[j]));
@@ -472,7 +508,7 @@ template <> struct KindT<CK_I8> { using T = int8_t; };
 
 template <int KIND, bool STATS, bool HLL>
 __device__ void numeric_range(const void* values, const uint32_t* validity, const uint32_t* mask,
-                              int64_t row0, int64_t row1, ColStats& s, int32_t* regs) {
+                              int64_t row0, int64_t row1, ColStats& s, int32_t* regs, uint32_t thr = 0) {
   using T = typename KindT<KIND>::T;
   constexpr bool kLazy = ck_float(KIND) && STATS;  // non-finite values found from the sums at the range's end
   const int lane = threadIdx.x & 63;
@@ -493,50 +529,59 @@ __device__ void numeric_range(const void* values, const uint32_t* validity, cons
       STATS ? range_shift(validity, mask, row0, row1, lane, [=](int64_t r) { return range_value<KIND>(vr, r - row0); }) : 0.0;
   int32_t qmin = 0;
   const int32_t nr = (int32_t)(row1 - row0);  // range-relative rows: 32-bit (scalar) loop control and compares
-  for (int32_t rb = 0; rb < nr; rb += kRowsPerIter) {
-    const int64_t base = row0 + rb + wave * 512;
-    const int32_t rem = nr - rb - wave * 512;  // rows of the range from this wave's block on
-    const bool full = rb + kRowsPerIter <= nr;
-    uint64_t bits[8], m[8];
-    double x[8];
-    const int32_t vo = (rb + wave * 512 + lane) * (int32_t)sizeof(T);
+  // The block loop, once per form of the HLL update (FLOOR: the floor test, numeric_block).  The choice is made
+  // per range, outside the loop: chosen per block, the two forms' accumulators meet in phi registers after
+  // every block (~1.1 v_mov per value on both paths, measured as +2.7 % VALU on the per-value path).
+  auto block_loop = [&](auto floor_form) __attribute__((always_inline)) {
+    constexpr bool FLOOR = decltype(floor_form)::value;
+    for (int32_t rb = 0; rb < nr; rb += kRowsPerIter) {
+      const int64_t base = row0 + rb + wave * 512;
+      const int32_t rem = nr - rb - wave * 512;  // rows of the range from this wave's block on
+      const bool full = rb + kRowsPerIter <= nr;
+      uint64_t bits[8], m[8];
+      double x[8];
+      const int32_t vo = (rb + wave * 512 + lane) * (int32_t)sizeof(T);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if constexpr (sizeof(T) == 8) {
-        const auto w2 = __builtin_amdgcn_raw_buffer_load_b64(vr, vo + j * 512, 0, 2 /* nt */);
-        bits[j] = ((uint64_t)w2[1] << 32) | w2[0];
-        if (KIND == CK_F64) x[j] = __builtin_bit_cast(double, bits[j]);
-        else x[j] = __builtin_fma((double)(int32_t)w2[1], 4294967296.0, (double)w2[0]);  // exact int64 -> double
-      } else if constexpr (KIND == CK_F32) {  // FloatType: Spark's Cast(child, DoubleType) is exact
-        const uint32_t w = __builtin_amdgcn_raw_buffer_load_b32(vr, vo + j * 256, 0, 2 /* nt */);
-        bits[j] = w;
-        x[j] = (double)__builtin_bit_cast(float, w);
-      } else {  // IntegerType / ShortType / ByteType: sign-extending loads (buffer_load_sshort / sbyte)
-        int32_t w;
-        if constexpr (sizeof(T) == 4) w = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(vr, vo + j * 256, 0, 2 /* nt */);
-        else if constexpr (sizeof(T) == 2) w = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(vr, vo + j * 128, 0, 2 /* nt */);
-        else w = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(vr, vo + j * 64, 0, 2 /* nt */);
-        bits[j] = (uint64_t)(int64_t)w;
-        x[j] = (double)w;
+      for (int j = 0; j < 8; ++j) {
+        if constexpr (sizeof(T) == 8) {
+          const auto w2 = __builtin_amdgcn_raw_buffer_load_b64(vr, vo + j * 512, 0, 2 /* nt */);
+          bits[j] = ((uint64_t)w2[1] << 32) | w2[0];
+          if (KIND == CK_F64) x[j] = __builtin_bit_cast(double, bits[j]);
+          else x[j] = __builtin_fma((double)(int32_t)w2[1], 4294967296.0, (double)w2[0]);  // exact int64 -> double
+        } else if constexpr (KIND == CK_F32) {  // FloatType: Spark's Cast(child, DoubleType) is exact
+          const uint32_t w = __builtin_amdgcn_raw_buffer_load_b32(vr, vo + j * 256, 0, 2 /* nt */);
+          bits[j] = w;
+          x[j] = (double)__builtin_bit_cast(float, w);
+        } else {  // IntegerType / ShortType / ByteType: sign-extending loads (buffer_load_sshort / sbyte)
+          int32_t w;
+          if constexpr (sizeof(T) == 4) w = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(vr, vo + j * 256, 0, 2 /* nt */);
+          else if constexpr (sizeof(T) == 2) w = (int16_t)__builtin_amdgcn_raw_buffer_load_b16(vr, vo + j * 128, 0, 2 /* nt */);
+          else w = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(vr, vo + j * 64, 0, 2 /* nt */);
+          bits[j] = (uint64_t)(int64_t)w;
+          x[j] = (double)w;
+        }
+      }
+      block_masks(validity, mask, base, rem, full, m);
+      // HLL-only fp64: one v_cmp_class per value (NaN or +-inf); only their OR stays live on the common path
+      // (keeping the 8 masks for the rare path spilled SGPRs into v_writelane / v_readlane on every block)
+      uint64_t nf_any = 0;
+      if constexpr (ck_float(KIND) && !kLazy) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) nf_any |= __builtin_amdgcn_ballot_w64(!__builtin_isfinite(x[j])) & m[j];
+      }
+      if (ck_float(KIND) && !kLazy && nf_any != 0) {
+        float_block_checked<KIND, STATS, HLL>(vr, validity, mask, base, rem, vo, shift, s, a, regs, cnt_w, nan_v, pinf_v,
+                                              ninf_v);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cnt_w += __builtin_popcountll(m[j]);
+        numeric_block<KIND, STATS, HLL, FLOOR>(x, bits, m, shift, s, a, regs, qmin, thr);
       }
     }
-    block_masks(validity, mask, base, rem, full, m);
-    // HLL-only fp64: one v_cmp_class per value (NaN or +-inf); only their OR stays live on the common path
-    // (keeping the 8 masks for the rare path spilled SGPRs into v_writelane / v_readlane on every block)
-    uint64_t nf_any = 0;
-    if constexpr (ck_float(KIND) && !kLazy) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) nf_any |= __builtin_amdgcn_ballot_w64(!__builtin_isfinite(x[j])) & m[j];
-    }
-    if (ck_float(KIND) && !kLazy && nf_any != 0) {
-      float_block_checked<KIND, STATS, HLL>(vr, validity, mask, base, rem, vo, shift, s, a, regs, cnt_w, nan_v, pinf_v,
-                                            ninf_v);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) cnt_w += __builtin_popcountll(m[j]);
-      numeric_block<KIND, STATS, HLL>(x, bits, m, shift, s, a, regs, qmin);
-    }
-  }
+  };
+  // (wave-uniform: the task's floor threshold, 0 = every value updates its register)
+  if (HLL && thr != 0) block_loop(std::true_type{});
+  else block_loop(std::false_type{});
   if constexpr (kLazy) {
     // a selected non-finite value (or an overflowing square) in any wave: the workgroup re-runs the range in
     // the checked form from fresh registers (the common pass hashed a NaN by its raw bits)
@@ -1294,28 +1339,29 @@ __device__ void run_numeric(const ColTask& t, const ScanCols& cols, const ScanBi
 template <int V, bool LONG>
 __device__ __forceinline__ void run_variant(const ColTask& t, const ScanCols& cols, const uint32_t* mask, int64_t row0,
                                             int64_t row1, int64_t n_rows, ColStats& s, int32_t* regs,
-                                            const uint64_t* p5, uint32_t* dq, uint32_t* rare, uint32_t* cls) {
+                                            const uint64_t* p5, uint32_t* dq, uint32_t* rare, uint32_t* cls,
+                                            uint32_t thr) {
   const void* v = cols.values[t.col];
   const uint32_t* val = cols.validity[t.col];
   if constexpr (V == CV_VALIDITY) validity_range(val, mask, row0, row1, s);
   else if constexpr (V == CV_F64_S) numeric_range<CK_F64, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_F64_SH) numeric_range<CK_F64, true, true>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_F64_H) numeric_range<CK_F64, false, true>(v, val, mask, row0, row1, s, regs);
+  else if constexpr (V == CV_F64_SH) numeric_range<CK_F64, true, true>(v, val, mask, row0, row1, s, regs, thr);
+  else if constexpr (V == CV_F64_H) numeric_range<CK_F64, false, true>(v, val, mask, row0, row1, s, regs, thr);
   else if constexpr (V == CV_I64_S) numeric_range<CK_I64, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I64_SH) numeric_range<CK_I64, true, true>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I64_H) numeric_range<CK_I64, false, true>(v, val, mask, row0, row1, s, regs);
+  else if constexpr (V == CV_I64_SH) numeric_range<CK_I64, true, true>(v, val, mask, row0, row1, s, regs, thr);
+  else if constexpr (V == CV_I64_H) numeric_range<CK_I64, false, true>(v, val, mask, row0, row1, s, regs, thr);
   else if constexpr (V == CV_I32_S) numeric_range<CK_I32, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I32_SH) numeric_range<CK_I32, true, true>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I32_H) numeric_range<CK_I32, false, true>(v, val, mask, row0, row1, s, regs);
+  else if constexpr (V == CV_I32_SH) numeric_range<CK_I32, true, true>(v, val, mask, row0, row1, s, regs, thr);
+  else if constexpr (V == CV_I32_H) numeric_range<CK_I32, false, true>(v, val, mask, row0, row1, s, regs, thr);
   else if constexpr (V == CV_F32_S) numeric_range<CK_F32, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_F32_SH) numeric_range<CK_F32, true, true>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_F32_H) numeric_range<CK_F32, false, true>(v, val, mask, row0, row1, s, regs);
+  else if constexpr (V == CV_F32_SH) numeric_range<CK_F32, true, true>(v, val, mask, row0, row1, s, regs, thr);
+  else if constexpr (V == CV_F32_H) numeric_range<CK_F32, false, true>(v, val, mask, row0, row1, s, regs, thr);
   else if constexpr (V == CV_I16_S) numeric_range<CK_I16, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I16_SH) numeric_range<CK_I16, true, true>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I16_H) numeric_range<CK_I16, false, true>(v, val, mask, row0, row1, s, regs);
+  else if constexpr (V == CV_I16_SH) numeric_range<CK_I16, true, true>(v, val, mask, row0, row1, s, regs, thr);
+  else if constexpr (V == CV_I16_H) numeric_range<CK_I16, false, true>(v, val, mask, row0, row1, s, regs, thr);
   else if constexpr (V == CV_I8_S) numeric_range<CK_I8, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I8_SH) numeric_range<CK_I8, true, true>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I8_H) numeric_range<CK_I8, false, true>(v, val, mask, row0, row1, s, regs);
+  else if constexpr (V == CV_I8_SH) numeric_range<CK_I8, true, true>(v, val, mask, row0, row1, s, regs, thr);
+  else if constexpr (V == CV_I8_H) numeric_range<CK_I8, false, true>(v, val, mask, row0, row1, s, regs, thr);
   else if constexpr (V == CV_F64_D) float_dtype_range(reinterpret_cast<const double*>(v), val, mask, row0, row1, s);
   else if constexpr (V == CV_F32_D) float_dtype_range(reinterpret_cast<const float*>(v), val, mask, row0, row1, s);
   else if constexpr (V == CV_BOOL) bool_range(reinterpret_cast<const uint32_t*>(v), val, mask, row0, row1, s, regs);
@@ -1356,7 +1402,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMinWave
                                                          int32_t part_base, ScanCols cols, ScanBitmaps bm,
                                                          int64_t n_rows, int64_t rows_per_range,
                                                          ColPartial* __restrict__ partials,
-                                                         uint32_t* __restrict__ hll_acc) {
+                                                         uint32_t* __restrict__ hll_acc,
+                                                         const uint32_t* __restrict__ hll_floor) {
   constexpr bool kHll = !(V == CV_VALIDITY || V == CV_F64_S || V == CV_I64_S || V == CV_I32_S || V == CV_F64_D ||
                          V == CV_UTF8_D || V == CV_LUTF8_D || V == CV_F32_S || V == CV_I16_S || V == CV_I8_S ||
                          V == CV_F32_D || V == CV_BOOL || V == CV_D128_S || V == CV_D128_D);
@@ -1393,7 +1440,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMinWave
   const uint32_t* mask = t.where >= 0 ? reinterpret_cast<const uint32_t*>(bm.where_bits[t.where]) : nullptr;
   const int32_t wv = kStr ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
   run_variant<V, LONG>(t, cols, mask, row0, row1, n_rows, s, regs, p5, dfq + wv * kDefFields * kDCap, rare + wv,
-                       clsbuf + (kCls ? wv * kClsWords : 0));
+                       clsbuf + (kCls ? wv * kClsWords : 0), kHll ? hll_floor_thr(hll_floor, t.hll_slot) : 0u);
   block_reduce_store(s, partials + (size_t)(part_base + ti) * kMaxWG + range, red);
   if constexpr (kStr) {
     // the task's rare-path rows for dq_scan's choice of variant (finalize publishes them to the host)
@@ -2004,7 +2051,9 @@ __global__ __launch_bounds__(kBlock) void dq_pred_scan(const PredProgram* __rest
 
 // ------------------------------------------------------------------------------------------
 // Kernel 4: fixed-order merge of per-workgroup partials into the plan accumulators.
-// blockIdx.x: [0, ncol) column tasks, [ncol, ncol + npair) pairs, then one block for counters.
+// blockIdx.x: [0, ncol) column tasks, [ncol, ncol + npair) pairs, then one block for counters (has_pred), then one
+// per HLL slot (nhll): the slot's floor for the next chunk's column scans (hll_floor_thr) -- every launch that
+// merges into hll_acc precedes this one on the plan's stream, so the floor is a function of the chunks scanned.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void dq_finalize(int32_t ncol, int32_t nranges_col,
                                                       const ColPartial* __restrict__ col_part,
@@ -2013,7 +2062,9 @@ __global__ __launch_bounds__(kBlock) void dq_finalize(int32_t ncol, int32_t nran
                                                       CorrPartial* __restrict__ pair_acc, int32_t has_pred,
                                                       int32_t nranges_pred, const PredPartial* __restrict__ pred_part,
                                                       PredPartial* __restrict__ pred_acc, FinRanges fr,
-                                                      int64_t* __restrict__ rare_dev, int64_t* rare_host) {
+                                                      int64_t* __restrict__ rare_dev, int64_t* rare_host,
+                                                      int32_t nhll, const uint32_t* __restrict__ hll_acc,
+                                                      uint32_t* __restrict__ hll_floor) {
   __shared__ ColStats cs[kBlock];
   __shared__ CorrStats ps[kBlock];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -2061,6 +2112,25 @@ __global__ __launch_bounds__(kBlock) void dq_finalize(int32_t ncol, int32_t nran
       CorrStats acc = {q.n, q.xa, q.ya, q.ck, q.xm, q.ym};
       corr_merge(acc, ps[0]);
       q.n = acc.n; q.xa = acc.xa; q.ya = acc.ya; q.ck = acc.ck; q.xm = acc.xm; q.ym = acc.ym;
+    }
+  } else if (b >= ncol + npair + (has_pred ? 1 : 0)) {
+    // min over the 512 registers of (max over the kHllCopies copies), accumulator encoding (0 = empty)
+    const int slot = b - (ncol + npair + (has_pred ? 1 : 0));
+    if (slot >= nhll) return;
+    __shared__ uint32_t fmin_w[kWaves];
+    const uint32_t* src = hll_acc + (size_t)slot * kHllCopies * 512;
+    uint32_t f = ~0u;
+    for (int i = tid; i < 512; i += kBlock) {
+      uint32_t r = 0;
+      for (int c = 0; c < kHllCopies; ++c) r = max(r, src[c * 512 + i]);
+      f = min(f, r);
+    }
+    for (int o = 32; o >= 1; o >>= 1) f = min(f, (uint32_t)__shfl_xor((int)f, o));
+    if ((tid & 63) == 0) fmin_w[tid >> 6] = f;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < kWaves; ++w) f = min(f, fmin_w[w]);
+      hll_floor[slot] = f;
     }
   } else if (has_pred) {
     // 256 threads = kMaxCounters counters x 8 range groups; integer sums are order-free
@@ -2114,27 +2184,29 @@ hipError_t launch_pred_scan(const PredProgram* prog, const ScanCols& cols, const
 template <int V>
 static void launch_v(const ColTask* tasks, int32_t ntasks, int32_t part_base, const ScanCols& cols,
                      const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range, int32_t nranges,
-                     ColPartial* partials, uint32_t* hll_acc, bool long_str, hipStream_t st) {
+                     ColPartial* partials, uint32_t* hll_acc, const uint32_t* hll_floor, bool long_str,
+                     hipStream_t st) {
   constexpr bool kStrHll = V == CV_UTF8_H || V == CV_LUTF8_H || V == CV_UTF8_HD || V == CV_LUTF8_HD;
   if constexpr (kStrHll) {
     if (long_str) {
       hipLaunchKernelGGL((dq_column_scan<V, true>), dim3((uint32_t)ntasks * (uint32_t)nranges), dim3(kBlock), 0, st,
-                         tasks, ntasks, part_base, cols, bm, n_rows, rows_per_range, partials, hll_acc);
+                         tasks, ntasks, part_base, cols, bm, n_rows, rows_per_range, partials, hll_acc, hll_floor);
       return;
     }
   }
   hipLaunchKernelGGL(dq_column_scan<V>, dim3((uint32_t)ntasks * (uint32_t)nranges), dim3(kBlock), 0, st, tasks, ntasks,
-                     part_base, cols, bm, n_rows, rows_per_range, partials, hll_acc);
+                     part_base, cols, bm, n_rows, rows_per_range, partials, hll_acc, hll_floor);
 }
 
 // tasks [first, first + ntasks) of the plan's task table all have variant `variant`
 hipError_t launch_column_scan(int32_t variant, const ColTask* tasks, int32_t ntasks, int32_t part_base,
                               const ScanCols& cols, const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range,
-                              int32_t nranges, ColPartial* partials, uint32_t* hll_acc, bool long_str, hipStream_t st) {
+                              int32_t nranges, ColPartial* partials, uint32_t* hll_acc, const uint32_t* hll_floor,
+                              bool long_str, hipStream_t st) {
 #define DQ_V(V)                                                                                            \
   case V:                                                                                                  \
-    launch_v<V>(tasks, ntasks, part_base, cols, bm, n_rows, rows_per_range, nranges, partials, hll_acc, long_str, \
-                st);                                                                                       \
+    launch_v<V>(tasks, ntasks, part_base, cols, bm, n_rows, rows_per_range, nranges, partials, hll_acc, hll_floor, \
+                long_str, st);                                                                             \
     break;
   switch (variant) {
     DQ_V(CV_VALIDITY) DQ_V(CV_F64_S) DQ_V(CV_F64_SH) DQ_V(CV_F64_H) DQ_V(CV_I64_S) DQ_V(CV_I64_SH) DQ_V(CV_I64_H)
@@ -2153,12 +2225,14 @@ hipError_t launch_column_scan(int32_t variant, const ColTask* tasks, int32_t nta
 hipError_t launch_finalize(int32_t ncol, int32_t nranges_col, const ColPartial* col_part, ColPartial* col_acc,
                            int32_t npair, int32_t nranges_pair, const CorrPartial* pair_part, CorrPartial* pair_acc,
                            int32_t has_pred, int32_t nranges_pred, const PredPartial* pred_part, PredPartial* pred_acc,
-                           const FinRanges& fr, int64_t* rare_dev, int64_t* rare_host, hipStream_t st) {
-  const uint32_t nb = (uint32_t)(ncol + npair + (has_pred ? 1 : 0));
+                           const FinRanges& fr, int64_t* rare_dev, int64_t* rare_host, int32_t nhll,
+                           const uint32_t* hll_acc, uint32_t* hll_floor, hipStream_t st) {
+  if (!hll_floor) nhll = 0;  // (the floor test switched off: no floors are kept)
+  const uint32_t nb = (uint32_t)(ncol + npair + (has_pred ? 1 : 0) + nhll);
   if (nb == 0) return hipSuccess;
   hipLaunchKernelGGL(dq_finalize, dim3(nb), dim3(kBlock), 0, st, ncol, nranges_col, col_part, col_acc, npair,
                      nranges_pair, pair_part, pair_acc, has_pred, nranges_pred, pred_part, pred_acc, fr, rare_dev,
-                     rare_host);
+                     rare_host, nhll, hll_acc, hll_floor);
   return hipGetLastError();
 }
 

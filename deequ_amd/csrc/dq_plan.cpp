@@ -60,7 +60,8 @@ hipError_t launch_pred_scan(const PredProgram* prog, const ScanCols& cols, const
                             bool has_regex);
 hipError_t launch_column_scan(int32_t variant, const ColTask* tasks, int32_t ntasks, int32_t part_base,
                               const ScanCols& cols, const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range,
-                              int32_t nranges, ColPartial* partials, uint32_t* hll_acc, bool long_str, hipStream_t st);
+                              int32_t nranges, ColPartial* partials, uint32_t* hll_acc, const uint32_t* hll_floor,
+                              bool long_str, hipStream_t st);
 hipError_t launch_pair_scan(const PairWG* wgs, int32_t nwg, const ScanCols& cols, const ScanBitmaps& bm,
                             const uint32_t* ones, int64_t n_rows, int64_t rows_per_range, int32_t nranges,
                             CorrPartial* pair_part, ColPartial* col_part, int32_t* redo, bool all_f64, bool ring,
@@ -69,7 +70,7 @@ hipError_t pair_scan_residency(bool all_f64, bool ring, bool minmax, int32_t* pe
 hipError_t launch_finalize(int32_t ncol, int32_t nranges_col, const ColPartial* col_part, ColPartial* col_acc,
                            int32_t npair, int32_t nranges_pair, const CorrPartial* pair_part, CorrPartial* pair_acc,
                            int32_t has_pred, int32_t nranges_pred, const PredPartial* pred_part, PredPartial* pred_acc, const FinRanges& fr, int64_t* rare_dev, int64_t* rare_host,
-                           hipStream_t st);
+                           int32_t nhll, const uint32_t* hll_acc, uint32_t* hll_floor, hipStream_t st);
 hipError_t launch_init_acc(ColPartial* col_acc, int32_t ncol, CorrPartial* pair_acc, int32_t npair, int64_t* rare_dev,
                            hipStream_t st);
 
@@ -703,6 +704,10 @@ struct dq_plan {
   PredPartial* d_pred_part = nullptr;
   ColPartial* d_col_acc = nullptr;
   uint32_t* d_hll_acc = nullptr;
+  // per HLL slot: the minimum register of d_hll_acc after the last finalize (0 after a reset); the next chunk's
+  // column scans skip the register updates that cannot exceed it.  Null with DQ_HLL_FLOOR=0 in the environment
+  // at plan creation: every value then updates its register.
+  uint32_t* d_hll_floor = nullptr;
   CorrPartial* d_pair_acc = nullptr;
   PredPartial* d_pred_acc = nullptr;
   uint64_t* d_where_bits[kMaxWhere] = {nullptr};
@@ -778,7 +783,7 @@ static dq_status free_plan_mem(dq_plan* p) {
   p->ev_pool.clear();
   void* ptrs[] = {p->d_col_tasks, p->d_pair_tasks, p->d_pair_wgs, p->d_prog, p->d_col_part, p->d_pair_part,
                   p->d_pred_part, p->d_col_acc, p->d_hll_acc, p->d_pair_acc, p->d_pred_acc, p->d_regex, p->d_pair_redo,
-                  p->d_rare_dev};
+                  p->d_rare_dev, p->d_hll_floor};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   for (int i = 0; i < kMaxWhere; ++i)
@@ -796,6 +801,7 @@ static dq_status reset_acc(dq_plan* p) {
   HIP_TRY(launch_init_acc(p->d_col_acc, (int32_t)p->col_tasks.size(), p->d_pair_acc, (int32_t)p->pair_tasks.size(),
                           p->d_rare_dev, p->stream));
   if (p->n_hll) HIP_TRY(hipMemsetAsync(p->d_hll_acc, 0, (size_t)p->n_hll * kHllCopies * 512 * sizeof(uint32_t), p->stream));
+  if (p->n_hll && p->d_hll_floor) HIP_TRY(hipMemsetAsync(p->d_hll_floor, 0, (size_t)p->n_hll * sizeof(uint32_t), p->stream));
   if (p->has_pred) HIP_TRY(hipMemsetAsync(p->d_pred_acc, 0, kPredAccCopies * sizeof(PredPartial), p->stream));
   if (p->total_rows > 0) p->prev_rows = p->total_rows;
   p->total_rows = 0;
@@ -1377,6 +1383,9 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   }
   (void)hipGetLastError();  // (no mapped memory: the fast variant throughout)
   if (dq_status s = dmalloc(&p->d_hll_acc, (size_t)p->n_hll * kHllCopies * 512 * sizeof(uint32_t))) return s;
+  const char* floor_env = std::getenv("DQ_HLL_FLOOR");
+  if (p->n_hll && !(floor_env && std::strcmp(floor_env, "0") == 0))
+    if (dq_status s = dmalloc(&p->d_hll_floor, (size_t)p->n_hll * sizeof(uint32_t))) return s;
   if (dq_status s = dmalloc(&p->d_pair_acc, npt * sizeof(CorrPartial))) return s;
   // (kPredAccCopies copies: the compiled predicate pass spreads its counter atomics over them; the host adds them)
   if (dq_status s = dmalloc(&p->d_pred_acc, kPredAccCopies * sizeof(PredPartial))) return s;
@@ -1988,8 +1997,8 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
     const auto& g = groups[gi];
     if (dq_status s = timed(p, 16 + g.variant, p->stream, [&] {
           return launch_column_scan(g.variant, p->d_col_tasks + g.first, g.count, g.first, sc, bm, n_rows,
-                                    vr[gi].first, vr[gi].second, p->d_col_part, p->d_hll_acc, str_long_of(g),
-                                    p->stream);
+                                    vr[gi].first, vr[gi].second, p->d_col_part, p->d_hll_acc, p->d_hll_floor,
+                                    str_long_of(g), p->stream);
         }))
       return s;
   }
@@ -2007,7 +2016,7 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
         return launch_finalize((int32_t)p->col_tasks.size(), nr_col, p->d_col_part, p->d_col_acc,
                                (int32_t)p->pair_tasks.size(), nr_pair, p->d_pair_part, p->d_pair_acc,
                                0 /* the predicate pass accumulates itself */, nr_pred, p->d_pred_part, p->d_pred_acc,
-                               fr, p->d_rare_dev, p->d_rare, p->stream);
+                               fr, p->d_rare_dev, p->d_rare, p->n_hll, p->d_hll_acc, p->d_hll_floor, p->stream);
       }))
     return s;
   p->total_rows += n_rows;
