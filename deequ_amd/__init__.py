@@ -14,6 +14,8 @@ from .grouping import (CountDistinct, Distinctness, Entropy, FrequenciesAndNumRo
                        MutualInformation, Uniqueness, UniqueValueRatio)
 from .metrics import (DoubleMetric, Distribution, DistributionValue, Entity, HistogramMetric,  # noqa: F401
                       KeyedDoubleMetric)
+from .profiles import (ColumnProfiler, ColumnProfiles, NumericColumnProfile, StandardColumnProfile,  # noqa: F401
+                       compute_histograms)
 from .quantiles import ApproxQuantile, ApproxQuantiles  # noqa: F401
 from .runner import AnalysisRunner, AnalyzerContext  # noqa: F401
 from .state_provider import HdfsStateProvider, InMemoryStateProvider  # noqa: F401

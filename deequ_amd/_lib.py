@@ -245,6 +245,17 @@ def _load():
     L.dq_freq_top.argtypes = [c.c_void_p, c.c_int32, P(c.c_uint64), P(c.c_int64), P(c.c_uint64), P(c.c_int32)]
     L.dq_freq_destroy.restype = None
     L.dq_freq_destroy.argtypes = [c.c_void_p]
+    L.dq_cat_hist_capacity.restype = c.c_int32
+    L.dq_cat_hist_capacity.argtypes = []
+    L.dq_cat_hist_build.restype = c.c_int32
+    L.dq_cat_hist_build.argtypes = [P(c.c_int32), c.c_int32, P(ColumnView), P(c.c_int64), c.c_int32, c.c_int32,
+                                    c.c_void_p, P(c.c_void_p)]
+    L.dq_cat_hist_column.restype = c.c_int32
+    L.dq_cat_hist_column.argtypes = [c.c_void_p, c.c_int32, P(c.c_int32), P(c.c_int64), P(c.c_int32)]
+    L.dq_cat_hist_export.restype = c.c_int32
+    L.dq_cat_hist_export.argtypes = [c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_int32]
+    L.dq_cat_hist_destroy.restype = None
+    L.dq_cat_hist_destroy.argtypes = [c.c_void_p]
     L.dq_plan_set_stream.restype = c.c_int32
     L.dq_plan_set_stream.argtypes = [c.c_void_p, c.c_void_p]
     L.dq_scan.restype = c.c_int32
@@ -312,6 +323,7 @@ EXPORTED = [
     "dq_plan_kernel_bytes_per_row_x1000", "dq_plan_pred_compiled", "dq_plan_pred_wait",
     "dq_state_merge", "dq_state_combine", "dq_state_merge_n", "dq_state_combine_n", "dq_state_is_defined", "dq_state_metric", "dq_hll_estimate",
     "dq_state_to_bytes", "dq_state_from_bytes", "dq_state_identifier", "dq_cast_utf8",
+    "dq_cat_hist_capacity", "dq_cat_hist_build", "dq_cat_hist_column", "dq_cat_hist_export", "dq_cat_hist_destroy",
 ]
 
 

@@ -30,6 +30,7 @@
 #include "dq_hash.h"
 #include "dq_internal.h"
 #include "dq_prim.h"
+#include "dq_strkey.h"
 
 namespace dq {
 namespace {
@@ -84,20 +85,7 @@ __device__ __forceinline__ const uint64_t* dec_at(const GroupCols& g, int c, int
 }
 
 __device__ __forceinline__ void str_of(const GroupCols& g, int c, int64_t r, const uint8_t*& p, int64_t& len) {
-  int64_t o0, o1;
-  if (g.type[c] == DQ_TYPE_LARGE_UTF8) {
-    o0 = reinterpret_cast<const int64_t*>(g.offsets[c])[r];
-    o1 = reinterpret_cast<const int64_t*>(g.offsets[c])[r + 1];
-  } else {
-    o0 = reinterpret_cast<const int32_t*>(g.offsets[c])[r];
-    o1 = reinterpret_cast<const int32_t*>(g.offsets[c])[r + 1];
-  }
-  p = reinterpret_cast<const uint8_t*>(g.values[c]) + o0;
-  len = o1 - o0;
-}
-
-__device__ __forceinline__ uint64_t mix8(uint64_t h, uint64_t k) {
-  return mul_add_c(rotl64(h ^ mul_add_c(k, XP2, 0), 27), XP1, XP4);
+  dq::str_of(g.values[c], g.offsets[c], g.type[c] == DQ_TYPE_LARGE_UTF8, r, p, len);
 }
 
 // 64-bit hash of the row's tuple (columns in order; strings by bytes and length)
@@ -108,19 +96,7 @@ __device__ uint64_t tuple_hash(const GroupCols& g, int64_t r, uint64_t seed = kS
       const uint8_t* p;
       int64_t len;
       str_of(g, c, r, p, len);
-      // little-endian words by (unaligned) 8- / 4-byte loads -- the same k as assembling the bytes one by one
-      typedef uint64_t u64u __attribute__((aligned(1)));
-      typedef uint32_t u32u __attribute__((aligned(1)));
-      int64_t i = 0;
-      for (; i + 8 <= len; i += 8) h = mix8(h, *reinterpret_cast<const u64u*>(p + i));
-      uint64_t k = 0;
-      int b = 0;
-      if (i + 4 <= len) {
-        k = *reinterpret_cast<const u32u*>(p + i);
-        b = 4;
-      }
-      for (; i + b < len; ++b) k |= (uint64_t)p[i + b] << (8 * b);
-      h = mix8(h, k ^ ((uint64_t)len << 56) ^ 0xA5);
+      h = mix_str(h, p, len);
     } else if (is_dec(g.type[c])) {
       const uint64_t* v = dec_at(g, c, r);
       h = mix8(mix8(h, v[0]), v[1]);
@@ -140,19 +116,7 @@ __device__ __forceinline__ bool tuple_equal_rows(const GroupCols& ga, const Grou
       str_of(ga, c, a, pa, la);
       str_of(gb, c, b, pb, lb);
       if (la != lb) return false;
-      // 8 bytes, then 4, then single bytes per step (gfx950 global loads take any byte address; none reads past
-      // either string): 8x fewer scattered loads than a byte loop (verify_runs over 1e8 C5 strings 17.4 ms, r4g3)
-      typedef uint64_t u64u __attribute__((aligned(1)));
-      typedef uint32_t u32u __attribute__((aligned(1)));
-      int64_t i = 0;
-      for (; i + 8 <= la; i += 8)
-        if (*reinterpret_cast<const u64u*>(pa + i) != *reinterpret_cast<const u64u*>(pb + i)) return false;
-      if (i + 4 <= la) {
-        if (*reinterpret_cast<const u32u*>(pa + i) != *reinterpret_cast<const u32u*>(pb + i)) return false;
-        i += 4;
-      }
-      for (; i < la; ++i)
-        if (pa[i] != pb[i]) return false;
+      if (!bytes_equal(pa, pb, la)) return false;
     } else if (is_dec(ga.type[c])) {
       const uint64_t *va = dec_at(ga, c, a), *vb = dec_at(gb, c, b);
       if (va[0] != vb[0] || va[1] != vb[1]) return false;
@@ -831,8 +795,7 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
   t->hashed = numeric1 && !mi ? 0 : 1;
 
   // test hook: keep only some bits of the primary tuple hash, to force collisions between distinct tuples
-  uint64_t key_mask = ~0ull;
-  if (const char* e = std::getenv("DQ_TEST_GROUP_HASH_MASK")) key_mask = std::strtoull(e, nullptr, 16);
+  const uint64_t key_mask = test_hash_mask();
   std::vector<GroupCols> gcs(std::max(1, n_chunks));
   for (int k = 0; k < n_chunks; ++k) {
     GroupCols& g = gcs[k];

@@ -37,7 +37,9 @@ extern "C" {
                                 per-plan capacities), AUTO compiles the predicate kernel in the background,
                                 dq_plan_pred_wait;
                              5: column types F32 / I16 / I8 / BOOL / DATE32 / TIMESTAMP (scan, predicates, Arrow import);
-                             6: DECIMAL128 (type codes carry precision / scale, dq_state Sum / Mean decimal partials) */
+                             6: DECIMAL128 (type codes carry precision / scale, dq_state Sum / Mean decimal partials);
+                                dq_cast_utf8 and the dq_cat_hist_* entry points are additions under 6 (nothing
+                                existing changed its layout or meaning) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -416,6 +418,30 @@ dq_status dq_freq_summarize(const dq_freq_table* t, int64_t num_rows, dq_freq_su
 int64_t dq_freq_num_groups(const dq_freq_table* t);
 dq_status dq_freq_export(const dq_freq_table* t, uint64_t* keys, int64_t* counts, int64_t cap);
 void dq_freq_destroy(dq_freq_table* t);
+/* ColumnProfiler.computeHistograms (profiles/ColumnProfiler.scala:518-565): the counts of every value of n_cols
+ * low-cardinality columns in one pass over the data -- what one dq_freq_build per column gives, without its sort,
+ * for columns the profiler's first pass found to hold few distinct values.  types: DQ_TYPE_UTF8 / LARGE_UTF8 / BOOL
+ * (anything else DQ_E_UNSUPPORTED: the profiler targets string and boolean columns, :498-511); cols: n_chunks x
+ * n_cols views, chunk-major, as dq_freq_build; n_cols at most 1024.  Every row counts once per column: a NULL row
+ * into n_null (the caller adds it to Histogram.NullFieldReplacement's bin), any other under its exact bytes (the
+ * empty string is a value) or its boolean value.  A string column holds at most dq_cat_hist_capacity() distinct
+ * non-null values: one with more has status 1 (over capacity), its counts are dropped (use dq_freq_build for it) and
+ * the other columns of the call are unaffected.  Strings are keyed by dq_freq_build's 64-bit tuple hash and every
+ * counted row's bytes are compared with its group's representative, within a chunk and across chunks: distinct
+ * values under one key fail the whole call with DQ_E_UNSUPPORTED and dq_freq_build's message, never a silent merge.
+ * dq_cat_hist_export: a column's n_values counts with, for a string column, one representative row id each (chunk
+ * << 40 | row: the value's first row, in ascending order, so two runs export the same arrays) whose bytes the caller
+ * renders; for a boolean column rep_rows holds the value itself, 0 (false) then 1 (true), present values only.
+ * No chunks, no rows or no columns give an empty, valid handle.  Synchronises hip_stream. */
+typedef struct dq_cat_hist dq_cat_hist;
+int32_t dq_cat_hist_capacity(void); /* distinct non-null values per column the fused pass holds */
+dq_status dq_cat_hist_build(const int32_t* types, int32_t n_cols, const dq_column_view* cols, const int64_t* chunk_rows,
+                            int32_t n_chunks, int32_t device, void* hip_stream, dq_cat_hist** out);
+dq_status dq_cat_hist_column(const dq_cat_hist* h, int32_t col, int32_t* status /* 0 ok, 1 over capacity */,
+                             int64_t* n_null, int32_t* n_values);
+dq_status dq_cat_hist_export(const dq_cat_hist* h, int32_t col, int64_t* counts, uint64_t* rep_rows /* chunk << 40 | row */,
+                             int32_t cap);
+void dq_cat_hist_destroy(dq_cat_hist* h);
 /* ApproxQuantile / ApproxQuantiles (analyzers/ApproxQuantile.scala:49-103, ApproxQuantiles.scala:30-105;
  * replaces their DeequFunctions.stateful_approx_quantile aggregation + PercentileDigest.getPercentiles).
  * One numeric column (DQ_TYPE_F64 / I64 / I32) over n_chunks chunk views; per quantile the exact order
