@@ -34,7 +34,8 @@ def decimal_type(precision: int, scale: int) -> int:
         raise ValueError(f"DecimalType({precision},{scale}) is not a GPU column type (precision 1..38, scale 0..p)")
     return TYPE_DECIMAL128 | precision << 8 | scale << 16
 
-# column-pass kernel variants (deequ_amd/csrc/dq_device.h ColVariant)
+# column-pass kernel variants (deequ_amd/csrc/dq_device.h ColVariant; the names are its kVariants table's, held
+# equal by tests/test_variant_table.py)
 VARIANT_NAMES = {0: "validity", 1: "f64_stats", 2: "f64_stats_hll", 3: "f64_hll", 4: "i64_stats",
                  5: "i64_stats_hll", 6: "i64_hll", 7: "i32_stats", 8: "i32_stats_hll", 9: "i32_hll",
                  10: "utf8_hll", 11: "large_utf8_hll", 12: "utf8_dtype", 13: "utf8_hll_dtype",

@@ -35,6 +35,7 @@ constexpr int kMaxRegexWords = 32768;       // compiled regex DFAs of one plan (
 // column kinds seen by the kernels (physical layouts: DATE32 columns are CK_I32, TIMESTAMP columns CK_I64 --
 // the planner's preconditions keep their non-numeric analyzers away)
 enum ColKind : int32_t {
+  CK_NONE = 0,  // a column-pass variant that reads no values (the validity bitmap only)
   CK_F64 = 1, CK_I64 = 2, CK_I32 = 3, CK_UTF8 = 4, CK_LUTF8 = 5,
   CK_F32 = 6, CK_I16 = 7, CK_I8 = 8, CK_BOOL = 9,  // (BOOL: LSB-first value bitmap)
   CK_D128 = 10,  // DecimalType: 16-byte two's-complement unscaled values (the column pass)
@@ -44,6 +45,9 @@ enum ColKind : int32_t {
   CK_D128_LO = 11, CK_D128_HI = 12, CK_D128_LOU = 13,
 };
 constexpr bool ck_float(int k) { return k == CK_F64 || k == CK_F32; }
+constexpr bool ck_numeric(int k) {  // the kinds numeric_range reads (values converted to double exactly)
+  return k == CK_F64 || k == CK_I64 || k == CK_I32 || k == CK_F32 || k == CK_I16 || k == CK_I8;
+}
 constexpr int ck_bytes(int k) {
   return k >= CK_D128 ? 16 : k == CK_F64 || k == CK_I64 ? 8 : k == CK_I32 || k == CK_F32 ? 4 : k == CK_I16 ? 2 : 1;
 }
@@ -69,6 +73,72 @@ enum ColVariant : int32_t {
   CV_D128_S = 28, CV_D128_SH = 29, CV_D128_H = 30, CV_D128_D = 31,
 };
 constexpr int kNumVariants = 32;
+
+// What each variant is: the one definition the kernels' dispatch (dq_kernels.hip run_variant / launch_column_scan),
+// the planner (dq_plan.cpp) and the tests read.  Row v describes ColVariant v: the kind of column it reads, what it
+// accumulates (stats = moments / sum / min / max, hll = HyperLogLog registers, dtype = the DataType counts) and its
+// short name (timer 16 + v, deequ_amd/_lib.py VARIANT_NAMES).  No two rows share (kind, stats, hll, dtype).
+struct VariantDesc {
+  int32_t variant;  // its own index (checked below: the rows are in ColVariant order)
+  int32_t kind;     // ColKind; CK_NONE: no values read
+  bool stats, hll, dtype;
+  const char* name;
+};
+inline constexpr VariantDesc kVariants[] = {
+    {CV_VALIDITY, CK_NONE, false, false, false, "validity"},
+    {CV_F64_S, CK_F64, true, false, false, "f64_stats"},
+    {CV_F64_SH, CK_F64, true, true, false, "f64_stats_hll"},
+    {CV_F64_H, CK_F64, false, true, false, "f64_hll"},
+    {CV_I64_S, CK_I64, true, false, false, "i64_stats"},
+    {CV_I64_SH, CK_I64, true, true, false, "i64_stats_hll"},
+    {CV_I64_H, CK_I64, false, true, false, "i64_hll"},
+    {CV_I32_S, CK_I32, true, false, false, "i32_stats"},
+    {CV_I32_SH, CK_I32, true, true, false, "i32_stats_hll"},
+    {CV_I32_H, CK_I32, false, true, false, "i32_hll"},
+    {CV_UTF8_H, CK_UTF8, false, true, false, "utf8_hll"},
+    {CV_LUTF8_H, CK_LUTF8, false, true, false, "large_utf8_hll"},
+    {CV_UTF8_D, CK_UTF8, false, false, true, "utf8_dtype"},
+    {CV_UTF8_HD, CK_UTF8, false, true, true, "utf8_hll_dtype"},
+    {CV_LUTF8_D, CK_LUTF8, false, false, true, "large_utf8_dtype"},
+    {CV_LUTF8_HD, CK_LUTF8, false, true, true, "large_utf8_hll_dtype"},
+    {CV_F64_D, CK_F64, false, false, true, "f64_dtype"},
+    {CV_F32_S, CK_F32, true, false, false, "f32_stats"},
+    {CV_F32_SH, CK_F32, true, true, false, "f32_stats_hll"},
+    {CV_F32_H, CK_F32, false, true, false, "f32_hll"},
+    {CV_I16_S, CK_I16, true, false, false, "i16_stats"},
+    {CV_I16_SH, CK_I16, true, true, false, "i16_stats_hll"},
+    {CV_I16_H, CK_I16, false, true, false, "i16_hll"},
+    {CV_I8_S, CK_I8, true, false, false, "i8_stats"},
+    {CV_I8_SH, CK_I8, true, true, false, "i8_stats_hll"},
+    {CV_I8_H, CK_I8, false, true, false, "i8_hll"},
+    {CV_F32_D, CK_F32, false, false, true, "f32_dtype"},
+    {CV_BOOL, CK_BOOL, false, true, false, "bool"},  // (selected / TRUE counts + the HLL hashes of true / false)
+    {CV_D128_S, CK_D128, true, false, false, "d128_stats"},
+    {CV_D128_SH, CK_D128, true, true, false, "d128_stats_hll"},
+    {CV_D128_H, CK_D128, false, true, false, "d128_hll"},
+    {CV_D128_D, CK_D128, false, false, true, "d128_dtype"},
+};
+// (v must be a ColVariant; in device code these are usable where v is a compile-time constant)
+constexpr int32_t cv_kind(int v) { return kVariants[v].kind; }
+constexpr bool cv_stats(int v) { return kVariants[v].stats; }
+constexpr bool cv_hll(int v) { return kVariants[v].hll; }
+constexpr bool cv_dtype(int v) { return kVariants[v].dtype; }
+constexpr bool cv_is_str(int v) { return cv_kind(v) == CK_UTF8 || cv_kind(v) == CK_LUTF8; }
+constexpr bool cv_is_str_hll(int v) { return cv_is_str(v) && cv_hll(v); }
+// the variant that reads `kind` and accumulates exactly (stats, hll, dtype), or -1
+constexpr int32_t cv_find(int kind, bool stats, bool hll, bool dtype) {
+  for (int v = 0; v < (int)(sizeof(kVariants) / sizeof(kVariants[0])); ++v)
+    if (kVariants[v].kind == kind && kVariants[v].stats == stats && kVariants[v].hll == hll && kVariants[v].dtype == dtype)
+      return v;
+  return -1;
+}
+constexpr bool cv_table_ok() {  // every row in its ColVariant slot and found by its own description
+  for (int v = 0; v < kNumVariants; ++v)
+    if (kVariants[v].variant != v || cv_find(cv_kind(v), cv_stats(v), cv_hll(v), cv_dtype(v)) != v) return false;
+  return true;
+}
+static_assert(sizeof(kVariants) / sizeof(kVariants[0]) == kNumVariants, "one kVariants row per ColVariant");
+static_assert(cv_table_ok(), "kVariants: a row out of ColVariant order, or two variants with one description");
 
 // per-variant row-range counts of one scan (dq_finalize merges nr[i] partials for tasks [first, end))
 // column-task ranges whose range count differs from the scan's default (string passes, the validity pass, a

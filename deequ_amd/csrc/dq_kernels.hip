@@ -17,6 +17,7 @@
 
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 
 #include "dq_device.h"
 #include "dq_hash.h"
@@ -728,22 +729,8 @@ struct DtCounts {
 constexpr int kStrAhead = DQ_STR_AHEAD;  // string windows in flight ahead of the one being hashed (1..7)
 constexpr uint32_t kDefCap = 128;  // < 64 left after a drain + <= 64 pushed per row group
 constexpr int kDefFields = 6;      // h lo, h hi, w4, w5, w6, len
-// Round 6: the short-string hash by stripe-count class.  The block loop loads and realigns
-// every string's window in row order as before, then pushes each selected string's window into one of two
-// per-wave LDS stacks -- class A: < 16 bytes (at most one 8-byte round), class B: 16..28 bytes (two, the third
-// deferred as before) -- and hashes a class 64 strings at a time once it holds 64: NULL rows never reach a
-// hash, and class A never runs the second round that a wave of mixed lengths otherwise runs for all 64 lanes.
-// Class A entries: the 16 window bytes with len in byte 15 (unused below 16 bytes); class B: bytes 0..27 + len.
-#ifndef DQ_STR_CLS
-#define DQ_STR_CLS 0
-#endif
-// Capacities: a class is hashed once it holds >= 64 (so < 64 are left); a push that would overflow it first
-// hashes what it holds (partial: only when one row group brings > kClsCap - 64 of a class, i.e. > 32).  96
-// entries per class and 96 deferred strings keep the string pass at 5 workgroups (waves per SIMD) per CU:
-// 5 x (4.4 KB + 4 x 6.75 KB) of the 160 KB LDS.
-constexpr uint32_t kClsCap = 96;
-constexpr uint32_t kClsWords = kClsCap * (4 + 8);     // per wave: A quads, then B's two quad arrays
-constexpr uint32_t kDefCapCls = 96;                   // the deferred queue of the class instantiation
+// (Hashing the short strings by stripe-count class from per-wave LDS stacks was built and measured in round 6 and
+// rejected -- DESIGN.md §7, profiles/r6_ab.txt; its code is no longer here.)
 
 // 32 bytes from byte `pos` of a window resource as little-endian dwords: three 16-byte loads from pos & ~3,
 // realigned with v_alignbyte
@@ -784,9 +771,7 @@ __device__ uint64_t xxh64_window_head(__amdgpu_buffer_rsrc_t rsrc, uint32_t rel,
 template <typename OffT, bool HLL, bool DT, bool LONG>
 __device__ void utf8_range(const uint8_t* data, const OffT* offsets, const uint32_t* validity,
                            const uint32_t* mask, int64_t row0, int64_t row1, int64_t n_rows, ColStats& s,
-                           int32_t* regs, const uint64_t* p5, uint32_t* dq, uint32_t* rare, uint32_t* cls) {
-  constexpr bool CLS = DQ_STR_CLS && HLL && !DT && !LONG;
-  constexpr uint32_t DCAP = CLS ? kDefCapCls : kDefCap;  // the deferred queue's capacity (its SoA stride)
+                           int32_t* regs, const uint64_t* p5, uint32_t* dq, uint32_t* rare) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (row0 >= row1) return;
@@ -920,10 +905,10 @@ __device__ void utf8_range(const uint8_t* data, const OffT* offsets, const uint3
   // high word does not carry it)
   auto drain = [&](uint32_t n) __attribute__((always_inline)) {
     if ((uint32_t)lane < n) {
-      const uint64_t h = ((uint64_t)dq[1 * DCAP + lane] << 32) | dq[0 * DCAP + lane];
-      const uint64_t k1 = ((uint64_t)dq[3 * DCAP + lane] << 32) | dq[2 * DCAP + lane];
-      const uint64_t b = xxh64_tail_head(xxh64_stripe_round(h, k1), (uint64_t)dq[4 * DCAP + lane],
-                                         dq[5 * DCAP + lane], bp);
+      const uint64_t h = ((uint64_t)dq[1 * kDefCap + lane] << 32) | dq[0 * kDefCap + lane];
+      const uint64_t k1 = ((uint64_t)dq[3 * kDefCap + lane] << 32) | dq[2 * kDefCap + lane];
+      const uint64_t b = xxh64_tail_head(xxh64_stripe_round(h, k1), (uint64_t)dq[4 * kDefCap + lane],
+                                         dq[5 * kDefCap + lane], bp);
       const HllKey key = hll_key_from_fmix(b);
       if (key.q >= 0) atomicMax(reinterpret_cast<int32_t*>(reinterpret_cast<char*>(regs) + key.addr), key.q);
       else hll_update(regs, fmix_tail(b));
@@ -936,75 +921,11 @@ __device__ void utf8_range(const uint8_t* data, const OffT* offsets, const uint3
     if ((uint32_t)lane < rest) {
       uint32_t v[kDefFields];
 #pragma unroll
-      for (int f = 0; f < kDefFields; ++f) v[f] = dq[f * DCAP + 64 + lane];
+      for (int f = 0; f < kDefFields; ++f) v[f] = dq[f * kDefCap + 64 + lane];
 #pragma unroll
-      for (int f = 0; f < kDefFields; ++f) dq[f * DCAP + lane] = v[f];
+      for (int f = 0; f < kDefFields; ++f) dq[f * kDefCap + lane] = v[f];
     }
     qtail = rest;
-  };
-  // class stacks (CLS): the wave's entries [0, qa) of class A and [0, qb) of class B
-  uint32_t qa = 0, qb = 0;
-  // hash n <= 64 entries [top, top + n) of class A (isb false: at most one 8-byte round) or B (two rounds; a string of
-  // 24..28 bytes goes on to the deferred queue for its third) -- one body for both classes (class A's lanes skip the
-  // second round, so its waves skip it): the row loop has one drain site per row group, like its inline hash had
-  auto cls_drain = [&](uint32_t top, uint32_t n, bool isb) __attribute__((always_inline)) {
-    const bool act = (uint32_t)lane < n;
-    uint32_t w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    uint32_t L = 0;
-    if (act) {
-      if (isb) {
-        const u32x4 q0 = reinterpret_cast<const u32x4*>(cls + 4 * kClsCap)[top + lane];
-        const u32x4 q1 = reinterpret_cast<const u32x4*>(cls + 8 * kClsCap)[top + lane];
-        w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z;
-        L = q1.w;
-      } else {
-        const u32x4 q = reinterpret_cast<const u32x4*>(cls)[top + lane];
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        L = q.w >> 24;
-      }
-    }
-    uint64_t d4p;
-    const uint64_t h2 = xxh64_stripes<2>(w, L, d4p);
-    const uint64_t dm = __builtin_amdgcn_ballot_w64(act && L >= 24u);
-    if (qtail + (uint32_t)__builtin_popcountll(dm) > DCAP) {  // (rare) make room: finish what the queue holds
-      drain(qtail);
-      qtail = 0;
-    }
-    if (dm != 0) {
-      const uint32_t pos = qtail + __builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u));
-      if (lane_bit(dm)) {
-        dq[0 * DCAP + pos] = (uint32_t)h2;
-        dq[1 * DCAP + pos] = (uint32_t)(h2 >> 32);
-        dq[2 * DCAP + pos] = (uint32_t)d4p;
-        dq[3 * DCAP + pos] = (uint32_t)(d4p >> 32);
-        dq[4 * DCAP + pos] = w[6];
-        dq[5 * DCAP + pos] = L;
-      }
-      qtail += (uint32_t)__builtin_popcountll(dm);
-    }
-    if (act && L < 24u) {
-      const uint64_t b = xxh64_tail_head(h2, d4p, L, bp);
-      const HllKey key = hll_key_from_fmix(b);
-      if (key.q >= 0) atomicMax(reinterpret_cast<int32_t*>(reinterpret_cast<char*>(regs) + key.addr), key.q);
-      else hll_update(regs, fmix_tail(b));
-    }
-  };
-  // drain what class A / B must give up before a push of na / nb entries: 64 once a class holds >= 64 (< 64 are
-  // left), or everything when the push would overflow kClsCap (only a class with < 64 and > kClsCap - na); one
-  // drain site (a rolled loop over the two classes)
-  auto cls_make_room = [&](uint32_t na, uint32_t nb) __attribute__((always_inline)) {
-    const uint32_t da = qa >= 64u ? 64u : (qa + na > kClsCap ? qa : 0u);
-    const uint32_t db = qb >= 64u ? 64u : (qb + nb > kClsCap ? qb : 0u);
-#pragma unroll 1
-    for (int c = 0; c < 2; ++c) {
-      const uint32_t n = c ? db : da;
-      if (n == 0) continue;
-      const uint32_t top = (c ? qb : qa) - n;
-      cls_drain(top, n, c != 0);
-      if (c) qb = top;
-      else qa = top;
-    }
-    if (qtail >= 64u) drain_full();
   };
   // every 32-byte window of the range lies inside the chunk's bytes iff its last row's does (offsets only
   // grow): then no row needs the per-row window compare (all but the chunk's last range; one scalar load --
@@ -1056,30 +977,7 @@ __device__ void utf8_range(const uint8_t* data, const OffT* offsets, const uint3
       for (int k = 0; k < 7; ++k) wv[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
       wv[7] = d[7];  // only ever feeds the unused half of the tail pair for len >= 24
       if constexpr (DT) dtc.add(dt_class_short(wv, len_of(j), lane_bit(m[j])), lane_bit(m[j]));
-      if constexpr (CLS) {
-        // push the row group's selected fast-path strings by class: rank among the pushing lanes, class A from
-        // qa up, class B from qb up (rank_B = rank - rank_A: one mbcnt pair less)
-        const uint32_t L = len_of(j);
-        const uint64_t mb = m[j] & __builtin_amdgcn_ballot_w64(L >= 16u);
-        const uint64_t ma = m[j] & ~mb;
-        cls_make_room((uint32_t)__builtin_popcountll(ma), (uint32_t)__builtin_popcountll(mb));
-        const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[j], 0u));
-        const uint32_t ra = __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, 0u));
-        if (lane_bit(ma)) {
-          u32x4 q;
-          q.x = wv[0]; q.y = wv[1]; q.z = wv[2]; q.w = (wv[3] & 0x00FFFFFFu) | (L << 24);
-          reinterpret_cast<u32x4*>(cls)[qa + ra] = q;
-        } else if (lane_bit(mb)) {
-          const uint32_t pb = qb + rk - ra;
-          u32x4 q0, q1;
-          q0.x = wv[0]; q0.y = wv[1]; q0.z = wv[2]; q0.w = wv[3];
-          q1.x = wv[4]; q1.y = wv[5]; q1.z = wv[6]; q1.w = L;
-          reinterpret_cast<u32x4*>(cls + 4 * kClsCap)[pb] = q0;
-          reinterpret_cast<u32x4*>(cls + 8 * kClsCap)[pb] = q1;
-        }
-        qa += (uint32_t)__builtin_popcountll(ma);
-        qb += (uint32_t)__builtin_popcountll(mb);
-      } else if constexpr (HLL) {
+      if constexpr (HLL) {
         uint64_t d4p;
         const uint64_t h2 = xxh64_stripes<2>(wv, len_of(j), d4p);
         const uint64_t dm = m[j] & __builtin_amdgcn_ballot_w64(len_of(j) >= 24u);  // needs the third round
@@ -1088,12 +986,12 @@ __device__ void utf8_range(const uint8_t* data, const OffT* offsets, const uint3
           // v_mov of it into the mbcnt)
           const uint32_t pos = qtail + __builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u));
           if (lane_bit(dm)) {
-            dq[0 * DCAP + pos] = (uint32_t)h2;
-            dq[1 * DCAP + pos] = (uint32_t)(h2 >> 32);
-            dq[2 * DCAP + pos] = (uint32_t)d4p;
-            dq[3 * DCAP + pos] = (uint32_t)(d4p >> 32);
-            dq[4 * DCAP + pos] = wv[6];
-            dq[5 * DCAP + pos] = len_of(j);
+            dq[0 * kDefCap + pos] = (uint32_t)h2;
+            dq[1 * kDefCap + pos] = (uint32_t)(h2 >> 32);
+            dq[2 * kDefCap + pos] = (uint32_t)d4p;
+            dq[3 * kDefCap + pos] = (uint32_t)(d4p >> 32);
+            dq[4 * kDefCap + pos] = wv[6];
+            dq[5 * kDefCap + pos] = len_of(j);
           }
           qtail += (uint32_t)__builtin_popcountll(dm);
         }
@@ -1140,10 +1038,6 @@ __device__ void utf8_range(const uint8_t* data, const OffT* offsets, const uint3
       if (lane == 0 && skipped) atomicAdd(rare, skipped);
       qmin = 0;
     }
-  }
-  if constexpr (CLS) {  // the classes' last entries (each <= kClsCap: one or two drains)
-#pragma unroll 1
-    while (qa | qb) cls_make_room(kClsCap, kClsCap);
   }
   if constexpr (HLL) {
     if (qtail != 0) drain(qtail);
@@ -1324,13 +1218,6 @@ __device__ void validity_range(const uint32_t* validity, const uint32_t* mask, i
   s.count += c;
 }
 
-template <int KIND, bool STATS, bool HLL>
-__device__ void run_numeric(const ColTask& t, const ScanCols& cols, const ScanBitmaps& bm, int64_t row0, int64_t row1,
-                            ColStats& s, int32_t* regs) {
-  const uint32_t* mask = t.where >= 0 ? reinterpret_cast<const uint32_t*>(bm.where_bits[t.where]) : nullptr;
-  numeric_range<KIND, STATS, HLL>(cols.values[t.col], cols.validity[t.col], mask, row0, row1, s, regs);
-}
-
 // ------------------------------------------------------------------------------------------
 // Kernel 2: single-column tasks.  One kernel instantiation per variant (kind x accumulators), so
 // each launch carries only its own inner loop (small I-cache footprint); the tasks of one variant
@@ -1339,44 +1226,23 @@ __device__ void run_numeric(const ColTask& t, const ScanCols& cols, const ScanBi
 template <int V, bool LONG>
 __device__ __forceinline__ void run_variant(const ColTask& t, const ScanCols& cols, const uint32_t* mask, int64_t row0,
                                             int64_t row1, int64_t n_rows, ColStats& s, int32_t* regs,
-                                            const uint64_t* p5, uint32_t* dq, uint32_t* rare, uint32_t* cls,
-                                            uint32_t thr) {
+                                            const uint64_t* p5, uint32_t* dq, uint32_t* rare, uint32_t thr) {
   const void* v = cols.values[t.col];
   const uint32_t* val = cols.validity[t.col];
-  if constexpr (V == CV_VALIDITY) validity_range(val, mask, row0, row1, s);
-  else if constexpr (V == CV_F64_S) numeric_range<CK_F64, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_F64_SH) numeric_range<CK_F64, true, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_F64_H) numeric_range<CK_F64, false, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I64_S) numeric_range<CK_I64, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I64_SH) numeric_range<CK_I64, true, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I64_H) numeric_range<CK_I64, false, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I32_S) numeric_range<CK_I32, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I32_SH) numeric_range<CK_I32, true, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I32_H) numeric_range<CK_I32, false, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_F32_S) numeric_range<CK_F32, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_F32_SH) numeric_range<CK_F32, true, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_F32_H) numeric_range<CK_F32, false, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I16_S) numeric_range<CK_I16, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I16_SH) numeric_range<CK_I16, true, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I16_H) numeric_range<CK_I16, false, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I8_S) numeric_range<CK_I8, true, false>(v, val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_I8_SH) numeric_range<CK_I8, true, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_I8_H) numeric_range<CK_I8, false, true>(v, val, mask, row0, row1, s, regs, thr);
-  else if constexpr (V == CV_F64_D) float_dtype_range(reinterpret_cast<const double*>(v), val, mask, row0, row1, s);
-  else if constexpr (V == CV_F32_D) float_dtype_range(reinterpret_cast<const float*>(v), val, mask, row0, row1, s);
-  else if constexpr (V == CV_BOOL) bool_range(reinterpret_cast<const uint32_t*>(v), val, mask, row0, row1, s, regs);
-  else if constexpr (V == CV_D128_S) decimal_range<true, false, false>(v, val, mask, row0, row1, s, regs, t.arg);
-  else if constexpr (V == CV_D128_SH) decimal_range<true, true, false>(v, val, mask, row0, row1, s, regs, t.arg);
-  else if constexpr (V == CV_D128_H) decimal_range<false, true, false>(v, val, mask, row0, row1, s, regs, t.arg);
-  else if constexpr (V == CV_D128_D) decimal_range<false, false, true>(v, val, mask, row0, row1, s, regs, t.arg);
-  else if constexpr (V == CV_UTF8_H || V == CV_UTF8_D || V == CV_UTF8_HD)
-    utf8_range<int32_t, V != CV_UTF8_D, V != CV_UTF8_H, LONG>(
-        reinterpret_cast<const uint8_t*>(v), reinterpret_cast<const int32_t*>(cols.offsets[t.col]), val, mask, row0,
-        row1, n_rows, s, regs, p5, dq, rare, cls);
-  else
-    utf8_range<int64_t, V != CV_LUTF8_D, V != CV_LUTF8_H, LONG>(
-        reinterpret_cast<const uint8_t*>(v), reinterpret_cast<const int64_t*>(cols.offsets[t.col]), val, mask, row0,
-        row1, n_rows, s, regs, p5, dq, rare, cls);
+  constexpr int K = cv_kind(V);
+  constexpr bool S = cv_stats(V), H = cv_hll(V), D = cv_dtype(V);
+  if constexpr (K == CK_NONE) validity_range(val, mask, row0, row1, s);
+  else if constexpr (ck_float(K) && D)
+    float_dtype_range(reinterpret_cast<const typename KindT<K>::T*>(v), val, mask, row0, row1, s);
+  else if constexpr (ck_numeric(K)) numeric_range<K, S, H>(v, val, mask, row0, row1, s, regs, thr);
+  else if constexpr (K == CK_BOOL) bool_range(reinterpret_cast<const uint32_t*>(v), val, mask, row0, row1, s, regs);
+  else if constexpr (K == CK_D128) decimal_range<S, H, D>(v, val, mask, row0, row1, s, regs, t.arg);
+  else {
+    static_assert(cv_is_str(V), "run_variant: a variant of a kind no case above reads");
+    using OffT = std::conditional_t<K == CK_UTF8, int32_t, int64_t>;
+    utf8_range<OffT, H, D, LONG>(reinterpret_cast<const uint8_t*>(v), reinterpret_cast<const OffT*>(cols.offsets[t.col]),
+                                 val, mask, row0, row1, n_rows, s, regs, p5, dq, rare);
+  }
 }
 
 // Minimum waves per SIMD the register allocator must leave room for (0 = no constraint); a
@@ -1390,8 +1256,7 @@ __device__ __forceinline__ void run_variant(const ColTask& t, const ScanCols& co
 #define DQ_NUM_WAVES 6
 #endif
 template <int V, bool LONG>
-constexpr int kMinWaves = V == CV_UTF8_H && !LONG && DQ_STR_CLS ? 5  // (the class stacks' LDS: 5 workgroups per CU)
-                          : V == CV_UTF8_H && DQ_STR_WAVES > 0 ? DQ_STR_WAVES
+constexpr int kMinWaves = V == CV_UTF8_H && DQ_STR_WAVES > 0 ? DQ_STR_WAVES
                           : (V == CV_F64_SH || V == CV_I64_SH) && DQ_NUM_WAVES > 0 ? DQ_NUM_WAVES
                           : V == CV_LUTF8_H && LONG ? 5  // (the register window would otherwise cost a wave)
                                                     : 1;
@@ -1404,18 +1269,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMinWave
                                                          ColPartial* __restrict__ partials,
                                                          uint32_t* __restrict__ hll_acc,
                                                          const uint32_t* __restrict__ hll_floor) {
-  constexpr bool kHll = !(V == CV_VALIDITY || V == CV_F64_S || V == CV_I64_S || V == CV_I32_S || V == CV_F64_D ||
-                         V == CV_UTF8_D || V == CV_LUTF8_D || V == CV_F32_S || V == CV_I16_S || V == CV_I8_S ||
-                         V == CV_F32_D || V == CV_BOOL || V == CV_D128_S || V == CV_D128_D);
-  constexpr bool kBool = V == CV_BOOL;  // (its two HLL hashes are constants: flags instead of registers)
-  constexpr bool kStr = V == CV_UTF8_H || V == CV_LUTF8_H || V == CV_UTF8_HD || V == CV_LUTF8_HD;
+  constexpr bool kBool = cv_kind(V) == CK_BOOL;  // (its two HLL hashes are constants: flags instead of registers)
+  constexpr bool kHll = cv_hll(V) && !kBool;
+  constexpr bool kStr = cv_is_str_hll(V);
   __shared__ int32_t regs[kHll ? 512 : 2];  // q = pw - 1, -1 = empty (see hll_q_exact); CV_BOOL: any TRUE / FALSE
   __shared__ uint64_t p5[kStr ? 256 : 1];   // b * P5 for the byte rounds of the string hash
-  constexpr uint32_t kDCap = DQ_STR_CLS && (V == CV_UTF8_H || V == CV_LUTF8_H) && !LONG ? kDefCapCls : kDefCap;
-  __shared__ uint32_t dfq[kStr ? kWaves * kDefFields * kDCap : 1];  // deferred 24..28-byte strings
+  __shared__ uint32_t dfq[kStr ? kWaves * kDefFields * kDefCap : 1];  // deferred 24..28-byte strings
   __shared__ uint32_t rare[kStr ? kWaves : 1];  // per wave: the rows the string fast path skipped
-  constexpr bool kCls = DQ_STR_CLS && (V == CV_UTF8_H || V == CV_LUTF8_H) && !LONG;
-  __shared__ __attribute__((aligned(16))) uint32_t clsbuf[kCls ? kWaves * kClsWords : 4];  // class stacks
   __shared__ ColStats red[kWaves];
   const int32_t ti = blockIdx.x % ntasks;
   const int32_t range = blockIdx.x / ntasks;
@@ -1439,8 +1299,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kMinWave
   stats_init(s);
   const uint32_t* mask = t.where >= 0 ? reinterpret_cast<const uint32_t*>(bm.where_bits[t.where]) : nullptr;
   const int32_t wv = kStr ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
-  run_variant<V, LONG>(t, cols, mask, row0, row1, n_rows, s, regs, p5, dfq + wv * kDefFields * kDCap, rare + wv,
-                       clsbuf + (kCls ? wv * kClsWords : 0), kHll ? hll_floor_thr(hll_floor, t.hll_slot) : 0u);
+  run_variant<V, LONG>(t, cols, mask, row0, row1, n_rows, s, regs, p5, dfq + wv * kDefFields * kDefCap, rare + wv,
+                       kHll ? hll_floor_thr(hll_floor, t.hll_slot) : 0u);
   block_reduce_store(s, partials + (size_t)(part_base + ti) * kMaxWG + range, red);
   if constexpr (kStr) {
     // the task's rare-path rows for dq_scan's choice of variant (finalize publishes them to the host)
@@ -2186,8 +2046,7 @@ static void launch_v(const ColTask* tasks, int32_t ntasks, int32_t part_base, co
                      const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range, int32_t nranges,
                      ColPartial* partials, uint32_t* hll_acc, const uint32_t* hll_floor, bool long_str,
                      hipStream_t st) {
-  constexpr bool kStrHll = V == CV_UTF8_H || V == CV_LUTF8_H || V == CV_UTF8_HD || V == CV_LUTF8_HD;
-  if constexpr (kStrHll) {
+  if constexpr (cv_is_str_hll(V)) {  // (the only variants with a LONG instantiation)
     if (long_str) {
       hipLaunchKernelGGL((dq_column_scan<V, true>), dim3((uint32_t)ntasks * (uint32_t)nranges), dim3(kBlock), 0, st,
                          tasks, ntasks, part_base, cols, bm, n_rows, rows_per_range, partials, hll_acc, hll_floor);
@@ -2198,26 +2057,21 @@ static void launch_v(const ColTask* tasks, int32_t ntasks, int32_t part_base, co
                      part_base, cols, bm, n_rows, rows_per_range, partials, hll_acc, hll_floor);
 }
 
+// launch_v<variant> for a run-time variant: a fold over Vs = 0 .. kNumVariants - 1, so every row of kVariants has
+// its instantiation (plus LONG for the string-HLL ones, in launch_v) and nothing else has; false: no such variant
+template <int... Vs, typename... Args>
+static bool launch_any(std::integer_sequence<int, Vs...>, int32_t variant, const Args&... args) {
+  return ((variant == Vs && (launch_v<Vs>(args...), true)) || ...);
+}
+
 // tasks [first, first + ntasks) of the plan's task table all have variant `variant`
 hipError_t launch_column_scan(int32_t variant, const ColTask* tasks, int32_t ntasks, int32_t part_base,
                               const ScanCols& cols, const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range,
                               int32_t nranges, ColPartial* partials, uint32_t* hll_acc, const uint32_t* hll_floor,
                               bool long_str, hipStream_t st) {
-#define DQ_V(V)                                                                                            \
-  case V:                                                                                                  \
-    launch_v<V>(tasks, ntasks, part_base, cols, bm, n_rows, rows_per_range, nranges, partials, hll_acc, hll_floor, \
-                long_str, st);                                                                             \
-    break;
-  switch (variant) {
-    DQ_V(CV_VALIDITY) DQ_V(CV_F64_S) DQ_V(CV_F64_SH) DQ_V(CV_F64_H) DQ_V(CV_I64_S) DQ_V(CV_I64_SH) DQ_V(CV_I64_H)
-    DQ_V(CV_I32_S) DQ_V(CV_I32_SH) DQ_V(CV_I32_H) DQ_V(CV_UTF8_H) DQ_V(CV_LUTF8_H)
-    DQ_V(CV_UTF8_D) DQ_V(CV_UTF8_HD) DQ_V(CV_LUTF8_D) DQ_V(CV_LUTF8_HD) DQ_V(CV_F64_D)
-    DQ_V(CV_F32_S) DQ_V(CV_F32_SH) DQ_V(CV_F32_H) DQ_V(CV_I16_S) DQ_V(CV_I16_SH) DQ_V(CV_I16_H)
-    DQ_V(CV_I8_S) DQ_V(CV_I8_SH) DQ_V(CV_I8_H) DQ_V(CV_F32_D) DQ_V(CV_BOOL)
-    DQ_V(CV_D128_S) DQ_V(CV_D128_SH) DQ_V(CV_D128_H) DQ_V(CV_D128_D)
-    default: return hipErrorInvalidValue;
-  }
-#undef DQ_V
+  if (!launch_any(std::make_integer_sequence<int, kNumVariants>{}, variant, tasks, ntasks, part_base, cols, bm, n_rows,
+                  rows_per_range, nranges, partials, hll_acc, hll_floor, long_str, st))
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -866,9 +866,8 @@ static void plan_pair_wgs(const dq_plan* p, const PairGroup& g, std::vector<Pair
   for (int c = 0; c < g.ncols; ++c)
     for (size_t t = 0; t < p->col_tasks.size(); ++t) {
       const ColTask& ct = p->col_tasks[t];
-      if (ct.col == g.cols[c] && ct.where == g.where && !fused[t] &&
-          (ct.variant == CV_F64_S || ct.variant == CV_I64_S || ct.variant == CV_I32_S || ct.variant == CV_F32_S ||
-           ct.variant == CV_I16_S || ct.variant == CV_I8_S)) {
+      if (ct.col == g.cols[c] && ct.where == g.where && !fused[t] && ck_numeric(cv_kind(ct.variant)) &&
+          cv_stats(ct.variant) && !cv_hll(ct.variant)) {  // a numeric column's stats-only task
         PairWaveTask& w = wg.wave[c % 2];
         const int k = (c - c % 2) / 2;
         w.mom_mask |= 1u << k;
@@ -946,7 +945,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
     return DQ_OK;
   };
   auto col_task = [&](int32_t col, int32_t bm, bool stats, bool hll, int32_t& t, bool dtype = false) -> dq_status {
-    // a double / float / decimal column's DataType count is a variant of its own (CV_F64_D / CV_F32_D / CV_D128_D)
+    // a double / float / decimal column's DataType count is a variant of its own (f64_dtype / f32_dtype / d128_dtype)
     auto key = std::make_tuple(col, bm, dtype && (is_floating(p->schema[col].type) || is_decimal(p->schema[col].type)) ? 1 : 0);
     auto it = col_task_of.find(key);
     if (it == col_task_of.end()) {
@@ -954,7 +953,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
       t = (int32_t)p->col_tasks.size();
       col_task_of[key] = t;
       ColTask ct{};
-      ct.col = col; ct.where = bm; ct.hll_slot = -1; ct.variant = CV_VALIDITY;
+      ct.col = col; ct.where = bm; ct.hll_slot = -1;  // (its variant: from its needs, below)
       p->col_tasks.push_back(ct);
       col_task_needs.push_back(Needs{});
     } else {
@@ -1076,26 +1075,16 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
     int32_t type = p->schema[ct.col].type;
     if (hll) ct.hll_slot = p->n_hll++;
     if (is_decimal(type)) ct.arg = DQ_DECIMAL_PRECISION(type) | DQ_DECIMAL_SCALE(type) << 8;
-    if (dtype && type == DQ_TYPE_F64) ct.variant = CV_F64_D;
-    else if (dtype && type == DQ_TYPE_F32) ct.variant = CV_F32_D;
-    else if (dtype && is_decimal(type)) ct.variant = CV_D128_D;
-    else if (!stats && !hll && !dtype) ct.variant = CV_VALIDITY;
-    else if (is_decimal(type)) ct.variant = stats && hll ? CV_D128_SH : (stats ? CV_D128_S : CV_D128_H);
-    else if (type == DQ_TYPE_UTF8) ct.variant = hll && dtype ? CV_UTF8_HD : (dtype ? CV_UTF8_D : CV_UTF8_H);
-    else if (type == DQ_TYPE_LARGE_UTF8) ct.variant = hll && dtype ? CV_LUTF8_HD : (dtype ? CV_LUTF8_D : CV_LUTF8_H);
-    else if (type == DQ_TYPE_BOOL) ct.variant = CV_BOOL;  // (HLL only: a boolean is not numeric)
-    else {
-      int base;
-      switch (kind_of(type)) {
-        case CK_F64: base = CV_F64_S; break;
-        case CK_I64: base = CV_I64_S; break;  // (+ TimestampType: hashLong of the micros)
-        case CK_F32: base = CV_F32_S; break;
-        case CK_I16: base = CV_I16_S; break;
-        case CK_I8: base = CV_I8_S; break;
-        default: base = CV_I32_S; break;  // (+ DateType: hashInt of the days)
-      }
-      ct.variant = base + (stats && hll ? 1 : (stats ? 0 : 2));
-    }
+    // the variant the table (dq_device.h kVariants) has for the column's kind and the task's needs.  (TimestampType
+    // is CK_I64: hashLong of the micros; DateType CK_I32: hashInt of the days.)
+    const int32_t kind = kind_of(type);
+    if (dtype && (is_floating(type) || is_decimal(type))) ct.variant = cv_find(kind, false, false, true);  // its own task
+    else if (!stats && !hll && !dtype) ct.variant = cv_find(CK_NONE, false, false, false);
+    else if (kind == CK_BOOL) ct.variant = cv_find(CK_BOOL, false, true, false);  // (HLL only: a boolean is not numeric)
+    else ct.variant = cv_find(kind, stats, hll, dtype);
+    if (ct.variant < 0)
+      return set_error(DQ_E_INVALID, "internal: no column-pass variant for column %d (type %d) with stats %d, hll %d, dtype %d",
+                       ct.col, type, (int)stats, (int)hll, (int)dtype);
   }
 
   // predicate program: roots in slot order, each followed by STORE
@@ -1160,7 +1149,9 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
       std::vector<int32_t> tasks;
       for (size_t t = 0; t < p->col_tasks.size() && hll.size() < 8; ++t) {
         const ColTask& ct = p->col_tasks[t];
-        if (ct.where >= 0 || (ct.variant != CV_F64_H && ct.variant != CV_I64_H && ct.variant != CV_I32_H)) continue;
+        const int32_t k = cv_kind(ct.variant);  // HLL-only tasks of the kinds the generated kernel hashes
+        if (ct.where >= 0 || cv_stats(ct.variant) || !cv_hll(ct.variant) || (k != CK_F64 && k != CK_I64 && k != CK_I32))
+          continue;
         for (size_t i = 0; i < slots.size(); ++i)
           if (slots[i] == ct.col) {
             hll.push_back(PredJitHll{(int32_t)i});
@@ -1305,7 +1296,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   std::vector<int> need_values(ncols, 0), need_validity(ncols, 0);
   for (const ColTask& ct : p->col_tasks) {
     need_validity[ct.col] = 1;
-    if (ct.variant != CV_VALIDITY) need_values[ct.col] = 1;
+    if (cv_kind(ct.variant) != CK_NONE) need_values[ct.col] = 1;
   }
   for (const PairTask& pt : p->pair_tasks) {
     need_values[pt.col_x] = need_values[pt.col_y] = 1;
@@ -1866,14 +1857,12 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
   // per-variant workgroup counts: the string hash balances better with twice the ranges (uneven string
   // lengths, deferred-round drains): utf8_hll 1.979 -> 1.949 ms per 125 M x 4 on the C5 headline (x3 1.963,
   // x4 1.965 ms); halving the fp64 hash's ranges measured no change
-  auto variant_scale = [](int32_t v) -> int32_t {
-    return v == CV_UTF8_H || v == CV_LUTF8_H || v == CV_UTF8_HD || v == CV_LUTF8_HD ? 2 : 1;
-  };
+  auto variant_scale = [](int32_t v) -> int32_t { return cv_is_str_hll(v) ? 2 : 1; };
   // and the fp64 hash with half the ranges: 1.437 -> 1.421 ms per 125 M rows x 8 (r5r; twice the ranges
   // 1.47 -> 1.52, r5q; the int64 hash: half 0.79 -> 0.79-0.80, a quarter 0.82)
-  auto variant_div = [](int32_t v) -> int32_t { return v == CV_F64_SH || v == CV_F64_H ? DQ_F64_HLL_DIV : 1; };
+  auto variant_div = [](int32_t v) -> int32_t { return cv_kind(v) == CK_F64 && cv_hll(v) ? DQ_F64_HLL_DIV : 1; };
   auto variant_min_rows = [](int32_t v) -> int64_t {
-    return v == CV_VALIDITY ? DQ_MIN_VALIDITY_RANGE_ROWS : DQ_MIN_RANGE_ROWS;
+    return cv_kind(v) == CK_NONE ? DQ_MIN_VALIDITY_RANGE_ROWS : DQ_MIN_RANGE_ROWS;
   };
   FinRanges fr{};
   std::vector<std::pair<int64_t, int32_t>> vr(groups.size());  // (rows per range, ranges) per variant group
@@ -1982,8 +1971,7 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
   // the string pass's variant for a task group (see dq_plan::h_rare): the published rare-path rows are since the
   // reset and may be a chunk behind (read without waiting); the choice only changes speed, never the result
   auto str_long_of = [&](const dq_plan::Group& g) -> bool {
-    if (g.variant != CV_UTF8_H && g.variant != CV_LUTF8_H && g.variant != CV_UTF8_HD && g.variant != CV_LUTF8_HD)
-      return false;
+    if (!cv_is_str_hll(g.variant)) return false;  // (the only variants with a LONG instantiation)
     if (p->str_path != 0) return p->str_path == 2;
     const int64_t rows = p->total_rows > 0 ? p->total_rows : p->prev_rows;
     bool any = false;
@@ -2311,7 +2299,7 @@ int64_t dq_plan_variant_bytes_per_row_x1000(const dq_plan* p, int32_t variant) {
     const ColTask& t = p->col_tasks[i];
     if (t.variant != variant) continue;
     const dq_column_desc& cd = p->schema[t.col];
-    if (t.variant != CV_VALIDITY) b += value_bytes_x1000(cd.type);
+    if (cv_kind(t.variant) != CK_NONE) b += value_bytes_x1000(cd.type);
     if (cd.nullable) b += 125;
     if (t.where >= 0) b += 125;
   }
