@@ -18,6 +18,7 @@ from .profiles import (ColumnProfiler, ColumnProfiles, NumericColumnProfile, Sta
                        compute_histograms)
 from .quantiles import ApproxQuantile, ApproxQuantiles  # noqa: F401
 from .runner import AnalysisRunner, AnalyzerContext  # noqa: F401
+from .schema import (RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator)  # noqa: F401
 from .state_provider import HdfsStateProvider, InMemoryStateProvider  # noqa: F401
 from .states import (ApproxCountDistinctState, CorrelationState, DataTypeHistogram, MaxState, MeanState,  # noqa: F401
                      MinState, NumMatches, NumMatchesAndCount, StandardDeviationState, SumState)

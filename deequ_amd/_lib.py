@@ -106,6 +106,17 @@ class ColumnView(ctypes.Structure):
                 ("reserved", ctypes.c_int64)]
 
 
+# RowLevelSchemaValidator column definitions (enum dq_schema_kind, dq_schema_column)
+SCHEMA_STRING, SCHEMA_INT, SCHEMA_DECIMAL, SCHEMA_TIMESTAMP = 1, 2, 3, 4
+
+
+class SchemaColumn(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("column", ctypes.c_int32), ("nullable", ctypes.c_int32),
+                ("has_min", ctypes.c_int32), ("has_max", ctypes.c_int32), ("min_value", ctypes.c_int32),
+                ("max_value", ctypes.c_int32), ("precision", ctypes.c_int32), ("scale", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("text", ctypes.c_char_p)]
+
+
 class _Size(ctypes.Structure):
     _fields_ = [("num_matches", ctypes.c_int64)]
 
@@ -242,6 +253,22 @@ def _load():
     L.dq_cast_utf8.restype = c.c_int32
     L.dq_cast_utf8.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_int32, c.c_void_p, c.c_void_p, c.c_int32,
                                c.c_void_p, P(c.c_int64)]
+    L.dq_schema_plan_create.restype = c.c_int32
+    L.dq_schema_plan_create.argtypes = [P(SchemaColumn), c.c_int32, P(c.c_void_p)]
+    L.dq_schema_plan_destroy.restype = None
+    L.dq_schema_plan_destroy.argtypes = [c.c_void_p]
+    L.dq_schema_validate.restype = c.c_int32
+    L.dq_schema_validate.argtypes = [c.c_void_p, P(c.c_int32), P(ColumnView), c.c_int32, c.c_int64, c.c_void_p,
+                                     c.c_void_p, P(c.c_void_p), P(c.c_void_p), c.c_int32, c.c_void_p, P(c.c_int64),
+                                     P(c.c_int64)]
+    L.dq_schema_check_host.restype = c.c_int32
+    L.dq_schema_check_host.argtypes = [c.c_void_p, P(c.c_void_p), P(c.c_void_p), P(c.c_void_p), c.c_int32, c.c_int64,
+                                       c.c_void_p, P(c.c_void_p), P(c.c_void_p)]
+    L.dq_take_index.restype = c.c_int32
+    L.dq_take_index.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_int32, c.c_void_p]
+    L.dq_take_rows.restype = c.c_int32
+    L.dq_take_rows.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
+                               c.c_void_p, c.c_void_p, P(c.c_int64), c.c_int32, c.c_void_p]
     L.dq_freq_top.restype = c.c_int32
     L.dq_freq_top.argtypes = [c.c_void_p, c.c_int32, P(c.c_uint64), P(c.c_int64), P(c.c_uint64), P(c.c_int32)]
     L.dq_freq_destroy.restype = None
@@ -325,6 +352,8 @@ EXPORTED = [
     "dq_state_merge", "dq_state_combine", "dq_state_merge_n", "dq_state_combine_n", "dq_state_is_defined", "dq_state_metric", "dq_hll_estimate",
     "dq_state_to_bytes", "dq_state_from_bytes", "dq_state_identifier", "dq_cast_utf8",
     "dq_cat_hist_capacity", "dq_cat_hist_build", "dq_cat_hist_column", "dq_cat_hist_export", "dq_cat_hist_destroy",
+    "dq_schema_plan_create", "dq_schema_plan_destroy", "dq_schema_validate", "dq_schema_check_host",
+    "dq_take_index", "dq_take_rows",
 ]
 
 

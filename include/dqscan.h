@@ -38,8 +38,8 @@ extern "C" {
                                 dq_plan_pred_wait;
                              5: column types F32 / I16 / I8 / BOOL / DATE32 / TIMESTAMP (scan, predicates, Arrow import);
                              6: DECIMAL128 (type codes carry precision / scale, dq_state Sum / Mean decimal partials);
-                                dq_cast_utf8 and the dq_cat_hist_* entry points are additions under 6 (nothing
-                                existing changed its layout or meaning) */
+                                dq_cast_utf8, the dq_cat_hist_* entry points and the dq_schema_* / dq_take_* entry
+                                points are additions under 6 (nothing existing changed its layout or meaning) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -481,6 +481,67 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
 dq_status dq_cast_utf8(int32_t src_type, const dq_column_view* src, int64_t n_rows, int32_t to_type,
                        void* out_values, uint8_t* out_validity, int32_t device, void* hip_stream,
                        int64_t* null_count);
+/* RowLevelSchemaValidator (schema/RowLevelSchemaValidator.scala:25-282): a declared schema over string columns,
+ * the per-row verdict m = toCNF(schema) (:225-281, a three-valued SQL boolean), the conforming rows cast to the
+ * declared types and the other rows untouched.  One dq_schema_column per ColumnDefinition, in the schema's order:
+ *   DQ_SCHEMA_STRING     has_min / has_max: minLength / maxLength against length(c) (UTF-8 characters);
+ *                        text: `matches` (NULL = none), tested as regexp_extract(c, p, 0) != "" (DQ_REGEX_EXTRACT_NONEMPTY)
+ *   DQ_SCHEMA_INT        has_min / has_max: minValue / maxValue against Cast(c, IntegerType) = UTF8String.toInt
+ *   DQ_SCHEMA_DECIMAL    precision, scale (0 <= scale <= precision <= 38): Cast(c, DecimalType(p, s)) IS NOT NULL
+ *   DQ_SCHEMA_TIMESTAMP  text: the SimpleDateFormat mask; unix_timestamp(c, mask) IS NOT NULL, session time zone UTC.
+ *                        Masks: fields y (3 letters or more), M (at most 2), d, H, m, s, each followed by a literal
+ *                        (a non-letter, non-digit ASCII character or 'quoted text') or the end of the mask
+ * nullable = 0 adds the clause c IS NOT NULL.  A row is TRUE, FALSE or -- only when no clause is FALSE and an INT
+ * column with has_min is NULL in it (:246 is `FALSE OR v >= min`) -- UNKNOWN; an UNKNOWN row belongs to neither
+ * output, as in the reference.  dq_schema_plan_create needs no device; DQ_E_UNSUPPORTED (reason in dq_last_error) for
+ * a regex outside the DFA subset or a mask outside the subset above.
+ * dq_schema_validate: one chunk.  types / cols: the chunk's n_cols columns (device views; a definition reads column
+ * `column`, which must be UTF8 / LARGE_UTF8).  valid_bitmap / invalid_bitmap: ceil(n_rows / 64) 64-bit words each
+ * (device, 8-byte aligned): bit r of the first is set iff m is TRUE for row r, of the second iff m is FALSE; bits
+ * past n_rows are written 0.  cast_values[d] / cast_validity[d] (device; NULL entries or NULL arrays: not
+ * materialised; ignored for STRING) receive definition d's cast of every row: int32, 16-byte unscaled decimal or
+ * int64 microseconds per row (16-byte aligned) and ceil(n_rows / 64) validity words.  A row's cast is its value for
+ * every TRUE row; a row past its first FALSE clause may hold 0 / NULL instead.  *num_valid / *num_invalid (host):
+ * the TRUE and FALSE rows.  Synchronises hip_stream.
+ * dq_schema_check_host: the same rules over host bytes, no device (tests): per column c data[c], int64 offsets[c]
+ * (n_rows + 1) and valid[c] (one byte per row; NULL array or entry: no NULL rows); verdict[r] = 1 TRUE, 0 FALSE,
+ * 2 UNKNOWN; cast_values[d] as above, cast_ok[d] one byte per row (NULL entries: skipped); every definition's cast
+ * is evaluated for every row. */
+enum dq_schema_kind { DQ_SCHEMA_STRING = 1, DQ_SCHEMA_INT = 2, DQ_SCHEMA_DECIMAL = 3, DQ_SCHEMA_TIMESTAMP = 4 };
+typedef struct dq_schema_column {
+  int32_t kind;       /* enum dq_schema_kind */
+  int32_t column;     /* index into the views of a chunk */
+  int32_t nullable;   /* isNullable */
+  int32_t has_min, has_max;
+  int32_t min_value, max_value;
+  int32_t precision, scale;
+  int32_t reserved;   /* 0 */
+  const char* text;   /* UTF-8: STRING `matches` or NULL; TIMESTAMP mask */
+} dq_schema_column;
+typedef struct dq_schema_plan dq_schema_plan;
+dq_status dq_schema_plan_create(const dq_schema_column* defs, int32_t n_defs, dq_schema_plan** out);
+void dq_schema_plan_destroy(dq_schema_plan* plan);
+dq_status dq_schema_validate(dq_schema_plan* plan, const int32_t* types, const dq_column_view* cols, int32_t n_cols,
+                             int64_t n_rows, uint64_t* valid_bitmap, uint64_t* invalid_bitmap, void* const* cast_values,
+                             uint8_t* const* cast_validity, int32_t device, void* hip_stream, int64_t* num_valid,
+                             int64_t* num_invalid);
+dq_status dq_schema_check_host(const dq_schema_plan* plan, const uint8_t* const* data, const int64_t* const* offsets,
+                               const uint8_t* const* valid, int32_t n_cols, int64_t n_rows, uint8_t* verdict,
+                               void* const* cast_values, uint8_t* const* cast_ok);
+/* Stable row compaction ("take"): the rows a bitmap selects, in source order.  dq_take_index: index[k] (device,
+ * n_selected entries) = the k-th selected row of selection (device, ceil(n_rows / 64) 64-bit words); n_selected must
+ * be the bitmap's popcount over the n_rows (DQ_E_INVALID otherwise, nothing written).  dq_take_rows: one column of
+ * any dq_type through such an index.  out_values: fixed-width types n_selected values (BOOL: ceil(n_selected / 64)
+ * 64-bit words), strings the bytes; values_capacity = its size in bytes.  out_validity (NULL: not wanted):
+ * ceil(n_selected / 64) 64-bit words, all set when src has no validity.  Strings: out_offsets receives n_selected + 1
+ * offsets of src's width and *data_bytes the bytes selected; with out_values NULL the call stops there (the sizing
+ * call).  All output buffers are device memory, values 16-byte and bitmaps / offsets 8-byte aligned; bytes past the
+ * result (the padding a column carries) are the caller's to clear.  Both synchronise hip_stream. */
+dq_status dq_take_index(const uint64_t* selection, int64_t n_rows, int64_t n_selected, int64_t* index, int32_t device,
+                        void* hip_stream);
+dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, const int64_t* index, int64_t n_selected,
+                       void* out_values, int64_t values_capacity, uint8_t* out_validity, void* out_offsets,
+                       int64_t* data_bytes, int32_t device, void* hip_stream);
 /* Histogram (analyzers/Histogram.scala:33-99): the n largest groups by count (ties in key order):
  * key, count and -- for a table built from data with hashed keys (strings) -- one representative row
  * id (chunk << 40 | row) whose value the caller renders; ~0 when not available (merged tables). */
