@@ -5,8 +5,8 @@ libdqscan.so: hand-written gfx950 HIP kernels behind the C ABI in include/dqscan
 is the host-side mirror of the reference's analyzer / state / runner API over that ABI.
 """
 from ._lib import DQError, lib  # noqa: F401  (fails loudly if libdqscan.so is missing)
-from .checks import (Check, CheckLevel, CheckStatus, ConstraintStatus, VerificationResult,  # noqa: F401
-                     VerificationSuite)
+from .checks import (Check, CheckLevel, CheckStatus, ConstrainableDataTypes, ConstraintStatus,  # noqa: F401
+                     VerificationResult, VerificationSuite)
 from .analyzers import (ApproxCountDistinct, Completeness, Compliance, Correlation, DataType,  # noqa: F401
                         DataTypeInstances, Maximum, Mean, Minimum, PatternMatch, Patterns, Size, StandardDeviation,
                         Sum)
@@ -19,6 +19,9 @@ from .profiles import (ColumnProfiler, ColumnProfiles, NumericColumnProfile, Sta
 from .quantiles import ApproxQuantile, ApproxQuantiles  # noqa: F401
 from .runner import AnalysisRunner, AnalyzerContext  # noqa: F401
 from .schema import (RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator)  # noqa: F401
+from .split import random_split  # noqa: F401
+from .suggestions import (ConstraintSuggestion, ConstraintSuggestionResult, ConstraintSuggestionRunner,  # noqa: F401
+                          ConstraintSuggestions, Rules, UniqueIfApproximatelyUniqueRule)
 from .state_provider import HdfsStateProvider, InMemoryStateProvider  # noqa: F401
 from .states import (ApproxCountDistinctState, CorrelationState, DataTypeHistogram, MaxState, MeanState,  # noqa: F401
                      MinState, NumMatches, NumMatchesAndCount, StandardDeviationState, SumState)

@@ -269,6 +269,11 @@ def _load():
     L.dq_take_rows.restype = c.c_int32
     L.dq_take_rows.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
                                c.c_void_p, c.c_void_p, P(c.c_int64), c.c_int32, c.c_void_p]
+    L.dq_split_rows.restype = c.c_int32
+    L.dq_split_rows.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_double, c.c_void_p, c.c_void_p, c.c_int32,
+                                c.c_void_p, P(c.c_int64), P(c.c_int64)]
+    L.dq_split_rows_host.restype = c.c_int32
+    L.dq_split_rows_host.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_double, c.c_void_p]
     L.dq_freq_top.restype = c.c_int32
     L.dq_freq_top.argtypes = [c.c_void_p, c.c_int32, P(c.c_uint64), P(c.c_int64), P(c.c_uint64), P(c.c_int32)]
     L.dq_freq_destroy.restype = None
@@ -310,6 +315,8 @@ def _load():
     L.dq_plan_pred_compiled.argtypes = [c.c_void_p, c.c_char_p, c.c_int32]
     L.dq_plan_pred_wait.restype = c.c_int32
     L.dq_plan_pred_wait.argtypes = [c.c_void_p, c.c_int32]
+    L.dq_pred_jit_drain.restype = None
+    L.dq_pred_jit_drain.argtypes = []
     L.dq_state_merge.restype = c.c_int32
     L.dq_state_merge.argtypes = [P(State), P(State), P(State)]
     L.dq_state_combine.restype = c.c_int32
@@ -336,6 +343,12 @@ def _load():
 
 lib = _load()
 
+# a background compile of a predicate kernel must not outlive the interpreter: at process exit hipRTC's compiler
+# (loaded on first use, so torn down before this library) goes away under it.  Python's atexit runs first.
+import atexit  # noqa: E402
+
+atexit.register(lib.dq_pred_jit_drain)
+
 # every symbol include/dqscan.h declares (checked by tests/test_boundary.py)
 EXPORTED = [
     "dq_abi_version", "dq_last_error", "dq_plan_create", "dq_plan_create_ex", "dq_plan_create_opts",
@@ -348,12 +361,12 @@ EXPORTED = [
     "dq_freq_export", "dq_freq_destroy", "dq_mutual_information", "dq_approx_quantiles", "dq_quantile_digest", "dq_freq_top", "dq_scan", "dq_finish",
     "dq_plan_reset", "dq_plan_destroy", "dq_plan_bytes_per_row_x1000", "dq_plan_num_launches",
     "dq_plan_enable_timing", "dq_plan_kernel_time", "dq_plan_variant_bytes_per_row_x1000",
-    "dq_plan_kernel_bytes_per_row_x1000", "dq_plan_pred_compiled", "dq_plan_pred_wait",
+    "dq_plan_kernel_bytes_per_row_x1000", "dq_plan_pred_compiled", "dq_plan_pred_wait", "dq_pred_jit_drain",
     "dq_state_merge", "dq_state_combine", "dq_state_merge_n", "dq_state_combine_n", "dq_state_is_defined", "dq_state_metric", "dq_hll_estimate",
     "dq_state_to_bytes", "dq_state_from_bytes", "dq_state_identifier", "dq_cast_utf8",
     "dq_cat_hist_capacity", "dq_cat_hist_build", "dq_cat_hist_column", "dq_cat_hist_export", "dq_cat_hist_destroy",
     "dq_schema_plan_create", "dq_schema_plan_destroy", "dq_schema_validate", "dq_schema_check_host",
-    "dq_take_index", "dq_take_rows",
+    "dq_take_index", "dq_take_rows", "dq_split_rows", "dq_split_rows_host",
 ]
 
 

@@ -6,9 +6,9 @@ with the required ones, run through AnalysisRunner.doAnalysisRun (ONE fused scan
 and every constraint's assertion is evaluated on the metrics (Check.scala:878-890,
 AnalysisBasedConstraint.scala:42-122).  This module mirrors the constraint methods whose analyzers are on
 the GPU path, with the reference's predicate strings (Check.scala:670-871), constraint names
-(Constraint.scala:83-536) and failure messages, so a check runs unchanged on the MI355X path.  Grouping
-constraints (isUnique, hasUniqueness, hasEntropy, ...) are the reference's grouping pass and are not
-mirrored here.
+(Constraint.scala:83-536) and failure messages, so a check runs unchanged on the MI355X path.  The grouping
+constraints (isUnique, hasUniqueness, hasEntropy, ...) and hasDataType are constraint factories over the analyzers of
+grouping.py and the DataType analyzer; they are what the suggested constraints of suggestions.py resolve to.
 """
 from __future__ import annotations
 
@@ -17,7 +17,9 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance, Correlation, Maximum, Mean, Minimum,
                         PatternMatch, Size, StandardDeviation, Sum)
-from .grouping import _java_double_to_string
+from .analyzers import DataType, DataTypeInstances
+from .grouping import (Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
+                       _java_double_to_string)
 from .runner import AnalysisRunner, AnalyzerContext
 
 
@@ -35,6 +37,15 @@ class CheckStatus(IntEnum):  # Check.scala:34-36 (Enumeration order: Success < W
 class ConstraintStatus(IntEnum):  # Constraint.scala:25-27
     Success = 0
     Failure = 1
+
+
+class ConstrainableDataTypes(IntEnum):  # ConstrainableDataTypes.scala:19-26
+    Null = 0
+    Fractional = 1
+    Integral = 2
+    Boolean = 3
+    String = 4
+    Numeric = 5  # union of integral and fractional
 
 
 MISSING_ANALYSIS = "Missing Analysis, can't run the constraint!"          # AnalysisBasedConstraint.scala:117
@@ -78,6 +89,11 @@ class AnalysisBasedConstraint:  # AnalysisBasedConstraint.scala:42-111
             msg += f" {self.hint}"
         return ConstraintResult(self, ConstraintStatus.Failure, msg, metric)
 
+    def __str__(self):  # the case class's toString (functions print as <function1>, Options as Some(..) / None)
+        picker = "Some(<function1>)" if self.value_picker else "None"
+        hint = f"Some({self.hint})" if self.hint is not None else "None"
+        return f"AnalysisBasedConstraint({self.analyzer},<function1>,{picker},{hint})"
+
 
 class NamedConstraint:  # Constraint.scala:40-69 (ConstraintDecorator keeps the name in the result)
     def __init__(self, inner: AnalysisBasedConstraint, name: str):
@@ -100,6 +116,37 @@ def _named(analyzer, assertion, kind: str, picker=None, hint=None) -> NamedConst
 
 def _is_one(v) -> bool:  # Check.IsOne
     return v == 1.0
+
+
+def ratio_types(ignore_unknown: bool, key_type: str, distribution) -> float:
+    """ratioTypes (Constraint.scala:589-613): the key type's share of the distribution's values, of the values that
+    are not Unknown when ignore_unknown; 0.0 when the key type has no values."""
+    entry = distribution.values.get(key_type)
+    if not ignore_unknown:
+        return 0.0 if entry is None else entry.ratio
+    absolute = 0 if entry is None else entry.absolute
+    if absolute == 0:
+        return 0.0
+    num_values = sum(v.absolute for v in distribution.values.values())
+    unknown = distribution.values.get(DataTypeInstances.Unknown)
+    return float(absolute) / float(num_values - (0 if unknown is None else unknown.absolute))
+
+
+def data_type_value_picker(dataType: ConstrainableDataTypes) -> Callable:
+    """dataTypeConstraint's valuePicker (Constraint.scala:556-567)."""
+    I, T = DataTypeInstances, ConstrainableDataTypes
+    if dataType == T.Null:
+        return lambda d: ratio_types(False, I.Unknown, d)
+    if dataType == T.Numeric:
+        return lambda d: ratio_types(True, I.Fractional, d) + ratio_types(True, I.Integral, d)
+    key = {T.Fractional: I.Fractional, T.Integral: I.Integral, T.Boolean: I.Boolean, T.String: I.String}[T(dataType)]
+    return lambda d: ratio_types(True, key, d)
+
+
+def data_type_constraint(column, dataType, assertion=_is_one, hint=None) -> AnalysisBasedConstraint:
+    """Constraint.dataTypeConstraint (Constraint.scala:548-571): the one factory that returns the bare
+    AnalysisBasedConstraint, so its name is that case class's toString."""
+    return AnalysisBasedConstraint(DataType(column), assertion, data_type_value_picker(dataType), hint)
 
 
 class CheckResult:  # Check.scala:39-42
@@ -202,6 +249,45 @@ class Check:  # Check.scala:59-902
         los, his = _java_double_to_string(lo), _java_double_to_string(hi)
         predicate = f"`{column}` IS NULL OR (`{column}` {left} {los} AND `{column}` {right} {his})"
         return self.satisfies(predicate, f"{column} between {los} and {his}", hint=vals.get("hint"))
+
+    # ---- constraints on the grouping analyzers and DataType (plain addConstraint: no .where) --------
+    def isUnique(self, column, hint=None):  # Check.scala:139-141
+        return self.addConstraint(_named(Uniqueness([column]), _is_one, "UniquenessConstraint", None, hint))
+
+    def isPrimaryKey(self, column, *columns):  # Check.scala:151-153
+        return self.addConstraint(_named(Uniqueness([column, *columns]), _is_one, "UniquenessConstraint"))
+
+    def hasUniqueness(self, columns, assertion, hint=None):  # Check.scala:176-221
+        return self.addConstraint(_named(Uniqueness(columns), assertion, "UniquenessConstraint", None, hint))
+
+    def hasDistinctness(self, columns, assertion, hint=None):  # Check.scala:232-238
+        return self.addConstraint(_named(Distinctness(columns), assertion, "DistinctnessConstraint", None, hint))
+
+    def hasUniqueValueRatio(self, columns, assertion, hint=None):  # Check.scala:249-256
+        a = UniqueValueRatio(columns)
+        # (Constraint.scala:254 leaves the name's parenthesis open)
+        return self.addConstraint(NamedConstraint(AnalysisBasedConstraint(a, assertion, None, hint),
+                                                  f"UniqueValueRatioConstraint({a}"))
+
+    def hasNumberOfDistinctValues(self, column, assertion, binningUdf=None, maxBins=Histogram.MaximumAllowedDetailBins,
+                                  hint=None):  # Check.scala:269-278, histogramBinConstraint (Constraint.scala:133-147)
+        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins), assertion, "HistogramBinConstraint",
+                                         lambda d: d.numberOfBins, hint))
+
+    def hasHistogramValues(self, column, assertion, binningUdf=None, maxBins=Histogram.MaximumAllowedDetailBins,
+                           hint=None):  # Check.scala:295-304
+        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins), assertion, "HistogramConstraint",
+                                         None, hint))
+
+    def hasEntropy(self, column, assertion, hint=None):  # Check.scala:353-360
+        return self.addConstraint(_named(Entropy(column), assertion, "EntropyConstraint", None, hint))
+
+    def hasMutualInformation(self, columnA, columnB, assertion, hint=None):  # Check.scala:371-379
+        return self.addConstraint(_named(MutualInformation(columnA, columnB), assertion, "MutualInformationConstraint",
+                                         None, hint))
+
+    def hasDataType(self, column, dataType, assertion=_is_one, hint=None):  # Check.scala:653-661
+        return self.addConstraint(data_type_constraint(column, dataType, assertion, hint))
 
     # ---- evaluation --------------------------------------------------------------------------------
     def evaluate(self, context: AnalyzerContext) -> CheckResult:  # Check.scala:878-890

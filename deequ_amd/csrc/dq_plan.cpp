@@ -2380,6 +2380,8 @@ int64_t dq_plan_explain(const dq_analyzer_spec* specs, int32_t n_specs, const dq
   return (int64_t)t.size() + 1;
 }
 
+void dq_pred_jit_drain(void) { pred_jit_drain(); }
+
 int32_t dq_plan_pred_wait(dq_plan* p, int32_t timeout_ms) {
   if (!p) return set_error(DQ_E_INVALID, "dq_plan_pred_wait: plan is NULL");
   if (!p->parts.empty()) {

@@ -821,6 +821,16 @@ hipError_t pred_jit_launch(hipFunction_t fn, const PredJitArgs& a, int32_t nrang
 }  // namespace dq
 
 namespace dq {
+void pred_jit_drain() {
+  std::vector<std::thread> threads;
+  {
+    std::lock_guard<std::mutex> lock(g_workers.mu);
+    threads.swap(g_workers.threads);
+  }
+  for (std::thread& t : threads)
+    if (t.joinable()) t.join();
+}
+
 bool pred_jit_pending(const PredJitRef& e) {
   if (!e) return false;
   std::lock_guard<std::mutex> lock(e->mu);

@@ -49,6 +49,7 @@ PredJitRef pred_jit_request(const std::string& src, int device, bool background,
 hipFunction_t pred_jit_poll(const PredJitRef& e, int32_t wait_ms, std::string& note);
 // true while the compile is still running
 bool pred_jit_pending(const PredJitRef& e);
+void pred_jit_drain();  // joins the background compiles started so far
 hipError_t pred_jit_launch(hipFunction_t fn, const PredJitArgs& a, int32_t nranges, hipStream_t st);
 
 }  // namespace dq

@@ -65,6 +65,29 @@ class ColumnProfiles:  # ColumnProfile.scala:60-62
     profiles: Dict[str, ColumnProfile]
     numRecords: int
 
+    @staticmethod
+    def toJson(columnProfiles: Sequence[ColumnProfile]) -> str:
+        """ColumnProfiles.toJson (ColumnProfile.scala:67-146).  As there, typeCounts is not written (the reference
+        builds its object and never adds it) and isDataTypeInferred is a string."""
+        import json
+
+        columns = []
+        for p in columnProfiles:
+            c = {"column": p.column, "dataType": p.dataType,
+                 "isDataTypeInferred": "true" if p.isDataTypeInferred else "false", "completeness": p.completeness,
+                 "approximateNumDistinctValues": p.approximateNumDistinctValues}
+            if p.histogram is not None:
+                c["histogram"] = [{"value": k, "count": v.absolute, "ratio": v.ratio}
+                                  for k, v in p.histogram.values.items()]
+            if isinstance(p, NumericColumnProfile):
+                for key, v in (("mean", p.mean), ("maximum", p.maximum), ("minimum", p.minimum), ("sum", p.sum),
+                               ("stdDev", p.stdDev)):
+                    if v is not None:
+                        c[key] = v
+                c["approxPercentiles"] = list(p.approxPercentiles or [])
+            columns.append(c)
+        return json.dumps({"columns": columns}, indent=2)
+
 
 @dataclass
 class GenericColumnStatistics:  # ColumnProfiler.scala:31-42

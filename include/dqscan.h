@@ -38,8 +38,8 @@ extern "C" {
                                 dq_plan_pred_wait;
                              5: column types F32 / I16 / I8 / BOOL / DATE32 / TIMESTAMP (scan, predicates, Arrow import);
                              6: DECIMAL128 (type codes carry precision / scale, dq_state Sum / Mean decimal partials);
-                                dq_cast_utf8, the dq_cat_hist_* entry points and the dq_schema_* / dq_take_* entry
-                                points are additions under 6 (nothing existing changed its layout or meaning) */
+                                dq_cast_utf8, the dq_cat_hist_* entry points, the dq_schema_* / dq_take_* / dq_split_*
+                                entry points and dq_pred_jit_drain are additions under 6 (nothing existing changed its layout or meaning) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -382,6 +382,10 @@ int32_t dq_plan_pred_compiled(const dq_plan* plan, char* note, int32_t cap);
  * then 1 when the next dq_scan runs the compiled kernel, 0 when the interpreter runs it (compile failed, not
  * eligible, no predicates), or a negative dq_status. */
 int32_t dq_plan_pred_wait(dq_plan* plan, int32_t timeout_ms);
+/* Join every background compile still running.  A host program calls it before the process starts to exit: hipRTC
+ * loads its compiler on first use, so at exit that compiler is torn down before this library's own join runs, and a
+ * compile still in flight would run into it.  deequ_amd registers it with Python's atexit. */
+void dq_pred_jit_drain(void);
 /* EXPLAIN of the plan dq_plan_create_opts would build, on the host only (no device, no allocation, no
  * compile): the launches per scan, the column-pass variants, the pair pass, the predicate program and -- when
  * the predicate pass would be compiled -- the generated kernel source.  Writes at most cap bytes (incl. the
@@ -542,6 +546,18 @@ dq_status dq_take_index(const uint64_t* selection, int64_t n_rows, int64_t n_sel
 dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, const int64_t* index, int64_t n_selected,
                        void* out_values, int64_t values_capacity, uint8_t* out_validity, void* out_offsets,
                        int64_t* data_bytes, int32_t device, void* hip_stream);
+/* Row-level random split (the train / test split of suggestions/ConstraintSuggestionRunner.scala:127-148).  Row r of
+ * the chunk has the global index g = row0 + r; h = XXH64 of g's 8 little-endian bytes under `seed`,
+ * u = (h >> 11) * 2^-53, and the row is a test row iff u < test_ratio, else a training row: a pure function of
+ * (seed, g), so a table splits the same way however it is chunked.  (Spark's randomSplit depends on the
+ * partitioning and is not reproduced.)  train_bitmap / test_bitmap: ceil(n_rows / 64) 64-bit words each (device,
+ * 8-byte aligned), LSB first, bits past n_rows written 0 -- the layout dq_take_index reads.  *num_train + *num_test
+ * (host) = n_rows.  n_rows = 0: DQ_OK, nothing written; test_ratio outside ]0, 1[ or NaN, row0 < 0: DQ_E_INVALID.
+ * Synchronises hip_stream.  dq_split_rows_host: the same draw on the CPU, no device (tests): is_test[r] = 1 / 0. */
+dq_status dq_split_rows(int64_t n_rows, int64_t row0, uint64_t seed, double test_ratio, uint64_t* train_bitmap,
+                        uint64_t* test_bitmap, int32_t device, void* hip_stream, int64_t* num_train,
+                        int64_t* num_test);
+dq_status dq_split_rows_host(int64_t n_rows, int64_t row0, uint64_t seed, double test_ratio, uint8_t* is_test);
 /* Histogram (analyzers/Histogram.scala:33-99): the n largest groups by count (ties in key order):
  * key, count and -- for a table built from data with hashed keys (strings) -- one representative row
  * id (chunk << 40 | row) whose value the caller renders; ~0 when not available (merged tables). */
