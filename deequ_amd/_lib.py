@@ -276,6 +276,19 @@ def _load():
     L.dq_split_rows_host.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_double, c.c_void_p]
     L.dq_freq_top.restype = c.c_int32
     L.dq_freq_top.argtypes = [c.c_void_p, c.c_int32, P(c.c_uint64), P(c.c_int64), P(c.c_uint64), P(c.c_int32)]
+    L.dq_freq_materialize.restype = c.c_int32
+    L.dq_freq_materialize.argtypes = [c.c_void_p, P(ColumnView), P(c.c_int64), c.c_int32]
+    L.dq_freq_self_contained.restype = c.c_int32
+    L.dq_freq_self_contained.argtypes = [c.c_void_p]
+    L.dq_freq_to_bytes.restype = c.c_int64
+    L.dq_freq_to_bytes.argtypes = [c.c_void_p, c.c_void_p, c.c_int64]
+    L.dq_freq_from_bytes.restype = c.c_int32
+    L.dq_freq_from_bytes.argtypes = [c.c_char_p, c.c_int64, c.c_int32, c.c_void_p, P(c.c_void_p)]
+    L.dq_freq_take_values.restype = c.c_int32
+    L.dq_freq_take_values.argtypes = [c.c_void_p, P(c.c_uint64), c.c_int32, c.c_int32, c.c_void_p, c.c_int64,
+                                      P(c.c_int64), P(c.c_int64)]
+    L.dq_freq_mutual_information.restype = c.c_int32
+    L.dq_freq_mutual_information.argtypes = [c.c_void_p, c.c_int64, P(c.c_double), P(c.c_int32)]
     L.dq_freq_destroy.restype = None
     L.dq_freq_destroy.argtypes = [c.c_void_p]
     L.dq_cat_hist_capacity.restype = c.c_int32
@@ -358,7 +371,8 @@ EXPORTED = [
     "dq_arrow_import", "dq_uploader_create", "dq_upload", "dq_upload_fence", "dq_upload_release", "dq_upload_sync",
     "dq_uploader_destroy",
     "dq_plan_set_stream", "dq_freq_build", "dq_freq_merge", "dq_freq_summarize", "dq_freq_num_groups",
-    "dq_freq_export", "dq_freq_destroy", "dq_mutual_information", "dq_approx_quantiles", "dq_quantile_digest", "dq_freq_top", "dq_scan", "dq_finish",
+    "dq_freq_export", "dq_freq_destroy", "dq_freq_materialize", "dq_freq_self_contained", "dq_freq_to_bytes",
+    "dq_freq_from_bytes", "dq_freq_take_values", "dq_freq_mutual_information", "dq_mutual_information", "dq_approx_quantiles", "dq_quantile_digest", "dq_freq_top", "dq_scan", "dq_finish",
     "dq_plan_reset", "dq_plan_destroy", "dq_plan_bytes_per_row_x1000", "dq_plan_num_launches",
     "dq_plan_enable_timing", "dq_plan_kernel_time", "dq_plan_variant_bytes_per_row_x1000",
     "dq_plan_kernel_bytes_per_row_x1000", "dq_plan_pred_compiled", "dq_plan_pred_wait", "dq_pred_jit_drain",

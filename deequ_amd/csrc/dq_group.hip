@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "dq_device.h"
+#include "dq_freq_image.h"
 #include "dq_hash.h"
 #include "dq_internal.h"
 #include "dq_prim.h"
@@ -475,6 +476,20 @@ struct DevBuf {
 
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256)); }
 
+// one column of a table's value store (owned: freed with it)
+struct StoreCol {
+  void* values = nullptr;      // the values (fixed width) or the strings' bytes
+  int64_t* offsets = nullptr;  // strings: n + 1 offsets into values
+  int64_t bytes = 0;           // length of values
+  StoreCol() = default;
+  StoreCol(const StoreCol&) = delete;
+  StoreCol& operator=(const StoreCol&) = delete;
+  ~StoreCol() {
+    if (values) (void)hipFree(values);
+    if (offsets) (void)hipFree(offsets);
+  }
+};
+
 }  // namespace
 }  // namespace dq
 
@@ -491,6 +506,12 @@ struct dq_freq_table {
   int64_t* d_counts = nullptr;
   uint64_t* d_rep = nullptr;  // hashed tables built from data: one row id (chunk << 40 | row) per group
   uint64_t* d_keys2 = nullptr;  // hashed tables: second tuple hash per group (merge collision check)
+  // The value store of a self-contained hashed table (dq_freq_materialize, dq_freq_merge of two such tables,
+  // dq_freq_from_bytes): per grouping column the n_groups representative values in group order, laid out as one more
+  // input chunk without validity -- a dense array of dq_freq_elem_size(type) bytes per value (a BOOL one byte), or
+  // int64 offsets[n_groups + 1] and the bytes for strings -- so that store_cols() reads group g's tuple as row g.
+  bool has_store = false;
+  StoreCol store[kMaxGroupCols];
   ~dq_freq_table() {
     if (d_keys) (void)hipFree(d_keys);
     if (d_keys2) (void)hipFree(d_keys2);
@@ -643,6 +664,166 @@ __global__ void gather_top(const uint32_t* __restrict__ idx, int32_t n, const ui
     orp[i] = rep ? rep[g] : ~0ull;
   }
 }
+
+// ---- the value store: gathers of representative tuples (dq_freq_materialize, dq_freq_merge, dq_freq_take_values) ----
+// A gather reads row ids (chunk << 40 | row) against an array of chunk descriptors: the caller's input chunks, or the
+// stores of one or two tables (a store is one more chunk; row = group).
+
+// every row id names a chunk below n_chunks and a row below its chunk's row count
+__global__ void rep_check(const uint64_t* __restrict__ rep, int64_t G, const int64_t* __restrict__ chunk_rows,
+                          int32_t n_chunks, int32_t* __restrict__ bad) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = rep[g], k = r >> kRowBits;
+    if (k >= (uint64_t)n_chunks || (int64_t)(r & ((1ull << kRowBits) - 1)) >= chunk_rows[k]) atomicOr(bad, 1);
+  }
+}
+
+// out[g] = column c's value at row id rep[g]; es = bytes per stored value (a bit-packed BOOL becomes one byte)
+__global__ void gather_fixed(const uint64_t* __restrict__ rep, int64_t G, const GroupCols* __restrict__ chunks, int c, int es,
+                             void* __restrict__ out) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = rep[g];
+    const GroupCols& gc = chunks[r >> kRowBits];
+    const int64_t lr = (int64_t)(r & ((1ull << kRowBits) - 1));
+    const void* v = gc.values[c];
+    if (gc.type[c] == DQ_TYPE_BOOL) {
+      reinterpret_cast<uint8_t*>(out)[g] = (uint8_t)((reinterpret_cast<const uint32_t*>(v)[lr >> 5] >> (lr & 31)) & 1u);
+    } else if (es == 16) {
+      reinterpret_cast<uint64_t*>(out)[2 * g] = reinterpret_cast<const uint64_t*>(v)[2 * lr];
+      reinterpret_cast<uint64_t*>(out)[2 * g + 1] = reinterpret_cast<const uint64_t*>(v)[2 * lr + 1];
+    } else if (es == 8) {
+      reinterpret_cast<uint64_t*>(out)[g] = reinterpret_cast<const uint64_t*>(v)[lr];
+    } else if (es == 4) {
+      reinterpret_cast<uint32_t*>(out)[g] = reinterpret_cast<const uint32_t*>(v)[lr];
+    } else if (es == 2) {
+      reinterpret_cast<uint16_t*>(out)[g] = reinterpret_cast<const uint16_t*>(v)[lr];
+    } else {
+      reinterpret_cast<uint8_t*>(out)[g] = reinterpret_cast<const uint8_t*>(v)[lr];
+    }
+  }
+}
+
+// lens[g] = byte length of string column c at row id rep[g] (random reads of the offsets); lens[G] = 0, so that the
+// exclusive sum over G + 1 entries leaves the offsets array, its last entry the byte total
+__global__ void gather_str_lens(const uint64_t* __restrict__ rep, int64_t G, const GroupCols* __restrict__ chunks, int c,
+                                int64_t* __restrict__ lens) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= G; g += (int64_t)gridDim.x * blockDim.x) {
+    int64_t len = 0;
+    if (g < G) {
+      const uint64_t r = rep[g];
+      const uint8_t* p;
+      str_of(chunks[r >> kRowBits], c, (int64_t)(r & ((1ull << kRowBits) - 1)), p, len);
+    }
+    lens[g] = len;
+  }
+}
+
+// one lane copies one short string: 8 bytes, then 4, then single bytes per step by unaligned loads and stores (as
+// mix_str reads them); nothing is read or written outside [p, p + len) / [d, d + len)
+__device__ __forceinline__ void copy_lane(uint8_t* __restrict__ d, const uint8_t* __restrict__ p, int64_t len) {
+  int64_t i = 0;
+  for (; i + 8 <= len; i += 8) *reinterpret_cast<strkey_u64u*>(d + i) = *reinterpret_cast<const strkey_u64u*>(p + i);
+  if (i + 4 <= len) {
+    *reinterpret_cast<strkey_u32u*>(d + i) = *reinterpret_cast<const strkey_u32u*>(p + i);
+    i += 4;
+  }
+  for (; i < len; ++i) d[i] = p[i];
+}
+// the wave copies one long string (d, p, len wave-uniform): single bytes up to the destination's next 8-byte
+// boundary, then 64 x 8 bytes per step (aligned stores, unaligned loads), then the last < 8 bytes
+__device__ __forceinline__ void copy_wave(uint8_t* __restrict__ d, const uint8_t* __restrict__ p, int64_t len, int lane) {
+  int64_t head = (int64_t)((8 - (reinterpret_cast<uintptr_t>(d) & 7)) & 7);
+  if (head > len) head = len;
+  if (lane < head) d[lane] = p[lane];
+  d += head;
+  p += head;
+  len -= head;
+  const int64_t body = len & ~(int64_t)7;
+  for (int64_t i = (int64_t)lane * 8; i < body; i += 512)
+    *reinterpret_cast<uint64_t*>(d + i) = *reinterpret_cast<const strkey_u64u*>(p + i);
+  if (body + lane < len) d[body + lane] = p[body + lane];
+}
+constexpr int kWaveCopyLen = 40;  // strings of at least this many bytes take the wave path (the sweep)
+// out[offs[g] ..) = the bytes of string column c at row id rep[g].  A wave takes 64 consecutive groups: each lane
+// copies its own string when it is shorter than wave_len; the longer ones are then copied one after the other by
+// the whole wave (their descriptors broadcast from the owning lane).
+__global__ __launch_bounds__(256) void gather_str_bytes(const uint64_t* __restrict__ rep, int64_t G,
+                                                        const GroupCols* __restrict__ chunks, int c,
+                                                        const int64_t* __restrict__ offs, uint8_t* __restrict__ out,
+                                                        int64_t wave_len) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;  // a multiple of 64: i0 is wave-uniform
+  for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; i0 < G; i0 += stride) {
+    const int64_t g = i0 + lane;
+    const uint8_t* p = nullptr;
+    uint8_t* d = out;
+    int64_t len = 0;
+    if (g < G) {
+      const uint64_t r = rep[g];
+      str_of(chunks[r >> kRowBits], c, (int64_t)(r & ((1ull << kRowBits) - 1)), p, len);
+      d = out + offs[g];
+    }
+    const bool coop = len >= wave_len;
+    if (!coop) copy_lane(d, p, len);
+    uint64_t m = __builtin_amdgcn_ballot_w64(coop);
+    while (m) {
+      const int src = __builtin_ctzll(m);
+      m &= m - 1;
+      const uint64_t sp = __shfl((unsigned long long)reinterpret_cast<uintptr_t>(p), src);
+      const uint64_t sd = __shfl((unsigned long long)reinterpret_cast<uintptr_t>(d), src);
+      const int64_t sl = (int64_t)__shfl((unsigned long long)len, src);
+      copy_wave(reinterpret_cast<uint8_t*>(sd), reinterpret_cast<const uint8_t*>(sp), sl, lane);
+    }
+  }
+}
+
+// merge of two self-contained hashed tables: as merge_gather_check, but members of a run of equal first hashes are
+// compared value by value through the two stores (chunks[0] = a's, chunks[1] = b's; position p of the concatenated
+// groups is row p of a, or row p - na of b)
+__device__ __forceinline__ uint64_t merge_row_id(uint64_t p, int64_t na) {
+  return p < (uint64_t)na ? p : ((1ull << kRowBits) | (p - (uint64_t)na));
+}
+__global__ void merge_gather_check_values(const uint64_t* __restrict__ k1s, const uint64_t* __restrict__ pos,
+                                          const uint64_t* __restrict__ k2, const int64_t* __restrict__ c, int64_t n,
+                                          int64_t na, const GroupCols* __restrict__ chunks, uint64_t* __restrict__ k2s,
+                                          int64_t* __restrict__ cs, int32_t* __restrict__ collision) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t p = pos[i];
+    k2s[i] = k2[p];
+    cs[i] = c[p];
+    if (i > 0 && k1s[i] == k1s[i - 1] && !tuple_equal(chunks, merge_row_id(p, na), merge_row_id(pos[i - 1], na)))
+      atomicOr(collision, 1);
+  }
+}
+__global__ void merge_row_ids(uint64_t* __restrict__ pos, int64_t n, int64_t na) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    pos[i] = merge_row_id(pos[i], na);
+}
+
+// MutualInformation from a self-contained two-column table: group g's per-column keys from the store (row g)
+__global__ void store_col_keys(GroupCols st, int64_t G, uint64_t* __restrict__ xk, uint64_t* __restrict__ yk) {
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
+    xk[g] = col_key(st, 0, g);
+    yk[g] = col_key(st, 1, g);
+  }
+}
+
+// idx[i] = the group whose key is want[i] (binary search of the table's ascending keys); a key the table lacks
+// raises *missing
+__global__ void find_groups(const uint64_t* __restrict__ want, int32_t n, const uint64_t* __restrict__ keys, int64_t G,
+                            uint64_t* __restrict__ idx, int32_t* __restrict__ missing) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = want[i];
+  int64_t lo = 0, hi = G - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  idx[i] = (uint64_t)lo;
+  if (G == 0 || keys[lo] != k) atomicOr(missing, 1);
+}
 }  // namespace
 }  // namespace dq
 
@@ -756,6 +937,59 @@ static dq_status dict_table(dq_freq_table* t, const uint64_t* keys, const uint64
   }
   t->n_groups = nd;
   *done = true;
+  return DQ_OK;
+}
+
+// the chunk descriptor of a table's value store: group g's tuple is row g (strings have int64 offsets, a BOOL is a byte)
+static GroupCols store_cols(const dq_freq_table* t) {
+  GroupCols g;
+  std::memset(&g, 0, sizeof(g));
+  g.n_cols = (int32_t)t->types.size();
+  g.key_mask = test_hash_mask();
+  for (int c = 0; c < g.n_cols; ++c) {
+    const int32_t ty = t->types[c];
+    g.values[c] = t->store[c].values;
+    g.offsets[c] = t->store[c].offsets;
+    g.type[c] = ty == DQ_TYPE_UTF8 ? DQ_TYPE_LARGE_UTF8 : ty == DQ_TYPE_BOOL ? DQ_TYPE_I8 : ty;
+  }
+  return g;
+}
+
+static int64_t wave_copy_len() {  // DQ_FREQ_WAVE_COPY: the lane / wave switch length of the string gather (sweeps)
+  const char* e = std::getenv("DQ_FREQ_WAVE_COPY");  // (read per call: tools/freq_state_bench.py sweeps it)
+  const long long v = e ? std::atoll(e) : 0;
+  return v > 0 ? v : kWaveCopyLen;
+}
+
+// Column c (type code `type`) of the tuples at row ids d_rep[0 .. G) of the chunks d_chunks, gathered into *out
+// (allocated here, owned by the caller's StoreCol).  The caller holds g_arena_mu and has checked the row ids.
+static dq_status gather_column(int D, hipStream_t S, const GroupCols* d_chunks, const uint64_t* d_rep, int64_t G, int c,
+                               int32_t type, StoreCol* out) {
+  const int es = dq_freq_elem_size(type);
+  if (es < 0) return set_error(DQ_E_TYPE, "frequency table: unknown type code %d", type);
+  if (es > 0) {
+    out->bytes = G * es;
+    GHIP(hipMalloc(&out->values, std::max<int64_t>(8, out->bytes)));
+    if (G > 0) {
+      hipLaunchKernelGGL(gather_fixed, dim3(grid_for(G)), dim3(256), 0, S, d_rep, G, d_chunks, c, es, out->values);
+      GHIP(hipGetLastError());
+    }
+    return DQ_OK;
+  }
+  DevBuf tmp(D, 62);
+  if (dq_status s = tmp.alloc(prim::scan_temp_bytes(G + 1))) return s;
+  GHIP(hipMalloc(&out->offsets, (G + 1) * 8));
+  hipLaunchKernelGGL(gather_str_lens, dim3(grid_for(G + 1)), dim3(256), 0, S, d_rep, G, d_chunks, c, out->offsets);
+  GHIP(hipGetLastError());
+  GHIP(prim::exclusive_sum_i64(out->offsets, out->offsets, G + 1, tmp.p, S));
+  GHIP(hipMemcpyAsync(&out->bytes, out->offsets + G, 8, hipMemcpyDeviceToHost, S));
+  GHIP(hipStreamSynchronize(S));
+  GHIP(hipMalloc(&out->values, std::max<int64_t>(8, out->bytes)));
+  if (G > 0 && out->bytes > 0) {
+    hipLaunchKernelGGL(gather_str_bytes, dim3(grid_for(G)), dim3(256), 0, S, d_rep, G, d_chunks, c, out->offsets,
+                       reinterpret_cast<uint8_t*>(out->values), wave_copy_len());
+    GHIP(hipGetLastError());
+  }
   return DQ_OK;
 }
 
@@ -914,52 +1148,39 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
   return DQ_OK;
 }
 
-static dq_status mi_from_joint(dq_freq_table* t, const uint64_t* sorted_keys, const uint64_t* sorted_rows, int64_t nv,
-                               const GroupCols* d_chunks, const MiRequest& mi) {
-  *mi.defined = 0;
-  *mi.value = 0.0;
-  if (nv == 0) return DQ_OK;  // sum over an empty join is NULL -> metricFromEmpty
-  const int D = t->device;
-  const hipStream_t S = t->stream;
-  DevBuf gk(D, 30), gc(D, 31), nruns(D, 32), starts(D, 33), rep(D, 34), xk(D, 35), yk(D, 36), idx(D, 37), sk(D, 38),
-      sidx(D, 39), head(D, 40), seg(D, 41), segsum(D, 42), px(D, 43), py(D, 44), tmp(D, 45), part(D, 46), res(D, 47),
-      coll(D, 48);
-  for (DevBuf* b : {&gk, &gc, &starts, &rep, &xk, &yk, &idx, &sk, &sidx, &segsum, &px, &py})
-    if (dq_status s = b->alloc(nv * 8)) return s;
+// the marginals and the sum over G joint groups (counts gc; group g's representative row id rep[g], per-column keys
+// xk / yk, idx[g] = g): shared by the one-pass path (rows of the input) and the state path (rows of the store)
+static dq_status mi_from_groups(int D, hipStream_t S, int64_t G, const int64_t* gc, const uint64_t* rep, const uint64_t* xk,
+                                const uint64_t* yk, const uint64_t* idx, const GroupCols* d_chunks, const MiRequest& mi) {
+  DevBuf sk(D, 38), sidx(D, 39), head(D, 40), seg(D, 41), segsum(D, 42), px(D, 43), py(D, 44), tmp(D, 45), part(D, 46),
+      res(D, 47), coll(D, 48);
+  for (DevBuf* b : {&sk, &sidx, &segsum, &px, &py})
+    if (dq_status s = b->alloc(G * 8)) return s;
   for (DevBuf* b : {&head, &seg})
-    if (dq_status s = b->alloc(nv * 4)) return s;
-  for (DevBuf* b : {&nruns, &res, &coll})
+    if (dq_status s = b->alloc(G * 4)) return s;
+  for (DevBuf* b : {&res, &coll})
     if (dq_status s = b->alloc(8)) return s;
   if (dq_status s = part.alloc(kSumBlocks * sizeof(double))) return s;
-  const size_t tb = std::max({prim::runs_temp_bytes(nv), prim::sort_temp_bytes(nv, 8), prim::scan_temp_bytes(nv)});
+  const size_t tb = std::max({prim::runs_temp_bytes(G), prim::sort_temp_bytes(G, 8), prim::scan_temp_bytes(G)});
   if (dq_status s = tmp.alloc(tb)) return s;
-  // joint groups: keys, counts and first positions of the runs of the sorted joint keys
-  GHIP(prim::runs(sorted_keys, nv, gk.as<uint64_t>(), starts.as<int64_t>(), gc.as<int64_t>(), nruns.as<int64_t>(), tmp.p, S));
-  int64_t G = 0;
-  GHIP(hipMemcpyAsync(&G, nruns.p, 8, hipMemcpyDeviceToHost, S));
-  GHIP(hipStreamSynchronize(S));
-  hipLaunchKernelGGL(mi_group_keys, dim3(grid_for(G)), dim3(256), 0, S, sorted_rows, starts.as<int64_t>(), G, d_chunks,
-                     rep.as<uint64_t>(), xk.as<uint64_t>(), yk.as<uint64_t>(), idx.as<uint64_t>());
-  GHIP(hipGetLastError());
   GHIP(hipMemsetAsync(coll.p, 0, 8, S));
   for (int c = 0; c < 2; ++c) {
-    GHIP(prim::sort_pairs((c == 0 ? xk : yk).as<uint64_t>(), sk.as<uint64_t>(), idx.as<uint64_t>(),
-                          sidx.as<uint64_t>(), 8, G, 0, 64, false, tmp.p, tb, S));
-    hipLaunchKernelGGL(mi_heads, dim3(grid_for(G)), dim3(256), 0, S, sk.as<uint64_t>(), sidx.as<uint64_t>(),
-                       rep.as<uint64_t>(), G, d_chunks, c, head.as<uint32_t>(), coll.as<int32_t>());
+    GHIP(prim::sort_pairs(c == 0 ? xk : yk, sk.as<uint64_t>(), idx, sidx.as<uint64_t>(), 8, G, 0, 64, false, tmp.p, tb, S));
+    hipLaunchKernelGGL(mi_heads, dim3(grid_for(G)), dim3(256), 0, S, sk.as<uint64_t>(), sidx.as<uint64_t>(), rep, G,
+                       d_chunks, c, head.as<uint32_t>(), coll.as<int32_t>());
     GHIP(hipGetLastError());
     GHIP(prim::inclusive_sum_u32(head.as<uint32_t>(), seg.as<uint32_t>(), G, tmp.p, S));
     GHIP(hipMemsetAsync(segsum.p, 0, G * 8, S));
-    hipLaunchKernelGGL(mi_segsum, dim3(grid_for(G)), dim3(256), 0, S, sidx.as<uint64_t>(), seg.as<uint32_t>(),
-                       gc.as<int64_t>(), G, segsum.as<unsigned long long>());
+    hipLaunchKernelGGL(mi_segsum, dim3(grid_for(G)), dim3(256), 0, S, sidx.as<uint64_t>(), seg.as<uint32_t>(), gc, G,
+                       segsum.as<unsigned long long>());
     GHIP(hipGetLastError());
     hipLaunchKernelGGL(mi_scatter, dim3(grid_for(G)), dim3(256), 0, S, sidx.as<uint64_t>(), seg.as<uint32_t>(),
                        segsum.as<unsigned long long>(), G, (c == 0 ? px : py).as<int64_t>());
     GHIP(hipGetLastError());
   }
   const int nb = (int)std::min<int64_t>(kSumBlocks, (G + 255) / 256);
-  hipLaunchKernelGGL(mi_part, dim3(nb), dim3(256), 0, S, gc.as<int64_t>(), px.as<int64_t>(), py.as<int64_t>(), G,
-                     mi.total, part.as<double>());
+  hipLaunchKernelGGL(mi_part, dim3(nb), dim3(256), 0, S, gc, px.as<int64_t>(), py.as<int64_t>(), G, mi.total,
+                     part.as<double>());
   GHIP(hipGetLastError());
   hipLaunchKernelGGL(mi_final, dim3(1), dim3(64), 0, S, part.as<double>(), nb, res.as<double>());
   GHIP(hipGetLastError());
@@ -970,6 +1191,32 @@ static dq_status mi_from_joint(dq_freq_table* t, const uint64_t* sorted_keys, co
   if (collided) return set_error(DQ_E_UNSUPPORTED, "dq_mutual_information: 64-bit key collision between distinct values");
   *mi.defined = 1;
   return DQ_OK;
+}
+
+static dq_status mi_from_joint(dq_freq_table* t, const uint64_t* sorted_keys, const uint64_t* sorted_rows, int64_t nv,
+                               const GroupCols* d_chunks, const MiRequest& mi) {
+  *mi.defined = 0;
+  *mi.value = 0.0;
+  if (nv == 0) return DQ_OK;  // sum over an empty join is NULL -> metricFromEmpty
+  const int D = t->device;
+  const hipStream_t S = t->stream;
+  DevBuf gk(D, 30), gc(D, 31), nruns(D, 32), starts(D, 33), rep(D, 34), xk(D, 35), yk(D, 36), idx(D, 37), tmp(D, 45);
+  for (DevBuf* b : {&gk, &gc, &starts, &rep, &xk, &yk, &idx})
+    if (dq_status s = b->alloc(nv * 8)) return s;
+  if (dq_status s = nruns.alloc(8)) return s;
+  // (sized for the marginals' sorts and scans over at most nv groups as well: mi_from_groups does not grow it)
+  const size_t tb = std::max({prim::runs_temp_bytes(nv), prim::sort_temp_bytes(nv, 8), prim::scan_temp_bytes(nv)});
+  if (dq_status s = tmp.alloc(tb)) return s;
+  // joint groups: keys, counts and first positions of the runs of the sorted joint keys
+  GHIP(prim::runs(sorted_keys, nv, gk.as<uint64_t>(), starts.as<int64_t>(), gc.as<int64_t>(), nruns.as<int64_t>(), tmp.p, S));
+  int64_t G = 0;
+  GHIP(hipMemcpyAsync(&G, nruns.p, 8, hipMemcpyDeviceToHost, S));
+  GHIP(hipStreamSynchronize(S));
+  hipLaunchKernelGGL(mi_group_keys, dim3(grid_for(G)), dim3(256), 0, S, sorted_rows, starts.as<int64_t>(), G, d_chunks,
+                     rep.as<uint64_t>(), xk.as<uint64_t>(), yk.as<uint64_t>(), idx.as<uint64_t>());
+  GHIP(hipGetLastError());
+  return mi_from_groups(D, S, G, gc.as<int64_t>(), rep.as<uint64_t>(), xk.as<uint64_t>(), yk.as<uint64_t>(),
+                        idx.as<uint64_t>(), d_chunks, mi);
 }
 
 dq_status dq_freq_build(const int32_t* types, int32_t n_cols, const dq_column_view* cols, const int64_t* chunk_rows,
@@ -1009,7 +1256,10 @@ dq_status dq_freq_merge(const dq_freq_table* a, const dq_freq_table* b, dq_freq_
   std::lock_guard<std::mutex> lock(g_arena_mu);
   const int D = a->device;
   DevBuf k_in(D, 10), c_in(D, 11), k_s(D, 12), c_s(D, 13), nruns(D, 14), tmp(D, 15), k2_in(D, 16), pos(D, 17),
-      pos_s(D, 18), k2_s(D, 19), coll(D, 23), kdrop(D, 24);
+      pos_s(D, 18), k2_s(D, 19), coll(D, 23), kdrop(D, 24), d_stores(D, 60), rep_out(D, 61);
+  // both inputs self-contained: the output is, and equal first hashes are settled by the values; else the second hash
+  // decides as before and the output carries no values
+  const bool stores = t->hashed && a->has_store && b->has_store;
   for (DevBuf* d : {&k_in, &c_in, &k_s, &c_s})
     if (dq_status s = d->alloc(std::max<int64_t>(1, n) * 8)) return s;
   if (dq_status s = nruns.alloc(8)) return s;
@@ -1060,9 +1310,19 @@ dq_status dq_freq_merge(const dq_freq_table* a, const dq_freq_table* b, dq_freq_
     GHIP(prim::sort_pairs(k_in.as<uint64_t>(), k_s.as<uint64_t>(), pos.as<uint64_t>(), pos_s.as<uint64_t>(), 8, n, 0, 64,
                           false, tmp.p, tb, t->stream));
     GHIP(hipMemsetAsync(coll.p, 0, 8, t->stream));
-    hipLaunchKernelGGL(merge_gather_check, dim3(grid_for(n)), dim3(256), 0, t->stream, k_s.as<uint64_t>(),
-                       pos_s.as<uint64_t>(), k2_in.as<uint64_t>(), c_in.as<int64_t>(), n, k2_s.as<uint64_t>(),
-                       c_s.as<int64_t>(), coll.as<int32_t>());
+    if (stores) {  // members of a run compared exactly, value by value, through the two stores
+      const GroupCols two[2] = {store_cols(a), store_cols(b)};
+      if (dq_status s = d_stores.alloc(sizeof(two))) return s;
+      GHIP(hipMemcpyAsync(d_stores.p, two, sizeof(two), hipMemcpyHostToDevice, t->stream));
+      GHIP(hipStreamSynchronize(t->stream));  // (two is on this frame)
+      hipLaunchKernelGGL(merge_gather_check_values, dim3(grid_for(n)), dim3(256), 0, t->stream, k_s.as<uint64_t>(),
+                         pos_s.as<uint64_t>(), k2_in.as<uint64_t>(), c_in.as<int64_t>(), n, a->n_groups,
+                         d_stores.as<GroupCols>(), k2_s.as<uint64_t>(), c_s.as<int64_t>(), coll.as<int32_t>());
+    } else {
+      hipLaunchKernelGGL(merge_gather_check, dim3(grid_for(n)), dim3(256), 0, t->stream, k_s.as<uint64_t>(),
+                         pos_s.as<uint64_t>(), k2_in.as<uint64_t>(), c_in.as<int64_t>(), n, k2_s.as<uint64_t>(),
+                         c_s.as<int64_t>(), coll.as<int32_t>());
+    }
     GHIP(hipGetLastError());
     // runs of equal first hashes (kdrop: their starts): counts added, the first second hash kept
     GHIP(prim::runs(k_s.as<uint64_t>(), n, t->d_keys, kdrop.as<int64_t>(), nullptr, nruns.as<int64_t>(), tmp.p, t->stream));
@@ -1074,6 +1334,22 @@ dq_status dq_freq_merge(const dq_freq_table* a, const dq_freq_table* b, dq_freq_
     GHIP(hipStreamSynchronize(t->stream));
     if (collided)
       return set_error(DQ_E_UNSUPPORTED, "dq_freq_merge: 64-bit tuple-hash collision between distinct values of the two tables");
+    if (stores) {
+      // every output group's tuple from the first member of its run, gathered from the two stores
+      if (dq_status s = rep_out.alloc(std::max<int64_t>(1, t->n_groups) * 8)) return s;
+      GHIP(prim::run_firsts_u64(pos_s.as<uint64_t>(), n, kdrop.as<int64_t>(), nruns.as<int64_t>(), rep_out.as<uint64_t>(),
+                                t->stream));
+      hipLaunchKernelGGL(merge_row_ids, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, rep_out.as<uint64_t>(),
+                         t->n_groups, a->n_groups);
+      GHIP(hipGetLastError());
+    }
+  }
+  if (stores) {
+    for (int c = 0; c < (int)t->types.size(); ++c)
+      if (dq_status s = gather_column(D, t->stream, d_stores.as<GroupCols>(), rep_out.as<uint64_t>(), t->n_groups, c,
+                                      t->types[c], &t->store[c]))
+        return s;
+    t->has_store = true;
   }
   GHIP(hipStreamSynchronize(t->stream));
   *out = guard.release();
@@ -1154,6 +1430,241 @@ dq_status dq_freq_top(const dq_freq_table* t, int32_t n, uint64_t* keys, int64_t
   GHIP(hipMemcpyAsync(counts, oc.p, (size_t)m * 8, hipMemcpyDeviceToHost, t->stream));
   GHIP(hipMemcpyAsync(rep_rows, orp.p, (size_t)m * 8, hipMemcpyDeviceToHost, t->stream));
   GHIP(hipStreamSynchronize(t->stream));
+  return DQ_OK;
+}
+
+int32_t dq_freq_self_contained(const dq_freq_table* t) { return t && (!t->hashed || t->has_store) ? 1 : 0; }
+
+dq_status dq_freq_materialize(dq_freq_table* t, const dq_column_view* cols, const int64_t* chunk_rows, int32_t n_chunks) {
+  if (!t) return set_error(DQ_E_INVALID, "dq_freq_materialize: NULL table");
+  if (!t->hashed || t->has_store) return DQ_OK;  // its keys are its values / already done
+  if (t->n_groups > 0 && !t->d_rep)
+    return set_error(DQ_E_STATE, "dq_freq_materialize: a hashed table without representative rows (merged without values)");
+  const int n_cols = (int)t->types.size();
+  if (n_chunks < 0 || n_chunks > kMaxGroupChunks || (n_chunks > 0 && (!cols || !chunk_rows)) ||
+      (t->n_groups > 0 && n_chunks == 0))
+    return set_error(DQ_E_INVALID, "dq_freq_materialize: bad chunks (%d for %lld groups)", n_chunks, (long long)t->n_groups);
+  std::vector<GroupCols> gcs(std::max(1, n_chunks));
+  std::memset(gcs.data(), 0, gcs.size() * sizeof(GroupCols));
+  for (int k = 0; k < n_chunks; ++k) {
+    if (chunk_rows[k] < 0 || chunk_rows[k] >= (1ll << kRowBits)) return set_error(DQ_E_INVALID, "chunk rows");
+    GroupCols& g = gcs[k];
+    g.n_cols = n_cols;
+    g.key_mask = ~0ull;
+    for (int c = 0; c < n_cols; ++c) {
+      const dq_column_view& v = cols[(size_t)k * n_cols + c];
+      g.values[c] = v.values;
+      g.offsets[c] = v.offsets;
+      g.type[c] = t->types[c];
+    }
+  }
+  GHIP(hipSetDevice(t->device));
+  std::lock_guard<std::mutex> lock(g_arena_mu);
+  const int D = t->device;
+  DevBuf d_chunks(D, 60), d_rows(D, 63), bad(D, 64);
+  if (dq_status s = d_chunks.alloc(gcs.size() * sizeof(GroupCols))) return s;
+  if (dq_status s = d_rows.alloc(std::max(1, n_chunks) * 8)) return s;
+  if (dq_status s = bad.alloc(8)) return s;
+  GHIP(hipMemcpyAsync(d_chunks.p, gcs.data(), gcs.size() * sizeof(GroupCols), hipMemcpyHostToDevice, t->stream));
+  if (t->n_groups > 0) {
+    // the views must cover every stored row id before anything is read through them
+    GHIP(hipMemcpyAsync(d_rows.p, chunk_rows, (size_t)n_chunks * 8, hipMemcpyHostToDevice, t->stream));
+    GHIP(hipMemsetAsync(bad.p, 0, 8, t->stream));
+    hipLaunchKernelGGL(rep_check, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, t->d_rep, t->n_groups,
+                       d_rows.as<int64_t>(), n_chunks, bad.as<int32_t>());
+    GHIP(hipGetLastError());
+    int32_t out_of_range = 0;
+    GHIP(hipMemcpyAsync(&out_of_range, bad.p, 4, hipMemcpyDeviceToHost, t->stream));
+    GHIP(hipStreamSynchronize(t->stream));
+    if (out_of_range)
+      return set_error(DQ_E_INVALID, "dq_freq_materialize: the chunks do not cover the table's representative rows "
+                                     "(not the views it was built from)");
+  }
+  StoreCol cols_out[kMaxGroupCols];
+  for (int c = 0; c < n_cols; ++c)
+    if (dq_status s = gather_column(D, t->stream, d_chunks.as<GroupCols>(), t->d_rep, t->n_groups, c, t->types[c], &cols_out[c]))
+      return s;
+  GHIP(hipStreamSynchronize(t->stream));
+  for (int c = 0; c < n_cols; ++c) {  // all columns or none
+    std::swap(t->store[c].values, cols_out[c].values);
+    std::swap(t->store[c].offsets, cols_out[c].offsets);
+    t->store[c].bytes = cols_out[c].bytes;
+  }
+  t->has_store = true;
+  return DQ_OK;
+}
+
+// the sections of t's image (offsets as FreqImageView), its total length returned
+static int64_t image_layout(const dq_freq_table* t, FreqImageView* v) {
+  const int n_cols = (int)t->types.size();
+  const int64_t G = t->n_groups;
+  v->n_cols = n_cols;
+  v->hashed = t->hashed;
+  v->n_groups = G;
+  v->n_values = t->n_values;
+  int64_t at = freq_image_header_bytes(n_cols);
+  v->keys = at;
+  v->counts = at + 8 * G;
+  v->keys2 = t->hashed ? at + 16 * G : 0;
+  at += (t->hashed ? 24 : 16) * G;
+  for (int c = 0; c < n_cols && t->hashed; ++c) {
+    v->types[c] = t->types[c];
+    if (t->store[c].offsets) {
+      v->col_offsets[c] = at + 8;
+      at += 8 + 8 * (G + 1);
+    }
+    v->col_values[c] = at;
+    v->col_bytes[c] = t->store[c].bytes;
+    at += freq_image_pad8(t->store[c].bytes);
+  }
+  return at;
+}
+
+int64_t dq_freq_to_bytes(const dq_freq_table* t, uint8_t* out, int64_t cap) {
+  if (!t) return set_error(DQ_E_INVALID, "dq_freq_to_bytes: NULL table");
+  if (t->hashed && !t->has_store)
+    return set_error(DQ_E_STATE, "dq_freq_to_bytes: the table does not own its values (dq_freq_materialize it first)");
+  FreqImageView v;
+  const int64_t size = image_layout(t, &v);
+  if (!out || cap < size) return size;
+  GHIP(hipSetDevice(t->device));
+  std::memset(out, 0, (size_t)size);
+  std::memcpy(out, "DQFT", 4);
+  const uint32_t head[3] = {kFreqImageVersion, kFreqImageOrder, (uint32_t)v.n_cols};
+  std::memcpy(out + 4, head, 12);
+  std::memcpy(out + 16, t->types.data(), 4 * (size_t)v.n_cols);
+  int64_t at = 16 + 4 * (int64_t)((v.n_cols + 1) & ~1);
+  const int32_t hashed = t->hashed;
+  std::memcpy(out + at, &hashed, 4);
+  std::memcpy(out + at + 8, &v.n_groups, 8);
+  std::memcpy(out + at + 16, &v.n_values, 8);
+  const int64_t G = v.n_groups;
+  const hipStream_t S = t->stream;
+  if (G > 0) {
+    GHIP(hipMemcpyAsync(out + v.keys, t->d_keys, G * 8, hipMemcpyDeviceToHost, S));
+    GHIP(hipMemcpyAsync(out + v.counts, t->d_counts, G * 8, hipMemcpyDeviceToHost, S));
+    if (t->hashed) GHIP(hipMemcpyAsync(out + v.keys2, t->d_keys2, G * 8, hipMemcpyDeviceToHost, S));
+  }
+  for (int c = 0; c < v.n_cols && t->hashed; ++c) {
+    if (v.col_offsets[c]) {
+      std::memcpy(out + v.col_offsets[c] - 8, &v.col_bytes[c], 8);
+      GHIP(hipMemcpyAsync(out + v.col_offsets[c], t->store[c].offsets, (G + 1) * 8, hipMemcpyDeviceToHost, S));
+    }
+    if (v.col_bytes[c] > 0)
+      GHIP(hipMemcpyAsync(out + v.col_values[c], t->store[c].values, v.col_bytes[c], hipMemcpyDeviceToHost, S));
+  }
+  GHIP(hipStreamSynchronize(S));
+  return size;
+}
+
+dq_status dq_freq_from_bytes(const uint8_t* bytes, int64_t n, int32_t device, void* hip_stream, dq_freq_table** out) {
+  if (!out) return set_error(DQ_E_INVALID, "dq_freq_from_bytes: out is NULL");
+  *out = nullptr;
+  FreqImageView v;
+  char err[256];
+  if (dq_status s = freq_image_parse(bytes, n, &v, err, sizeof(err))) return set_error(s, "%s", err);
+  GHIP(hipSetDevice(device));
+  auto* t = new dq_freq_table();
+  std::unique_ptr<dq_freq_table> guard(t);
+  t->device = device;
+  t->stream = reinterpret_cast<hipStream_t>(hip_stream);
+  t->hashed = v.hashed;
+  t->types.assign(v.types, v.types + v.n_cols);
+  t->n_groups = v.n_groups;
+  t->n_values = v.n_values;
+  const int64_t G = v.n_groups;
+  const hipStream_t S = t->stream;
+  GHIP(hipMalloc(&t->d_keys, std::max<int64_t>(1, G) * 8));
+  GHIP(hipMalloc(&t->d_counts, std::max<int64_t>(1, G) * 8));
+  if (t->hashed) GHIP(hipMalloc(&t->d_keys2, std::max<int64_t>(1, G) * 8));
+  if (G > 0) {
+    GHIP(hipMemcpyAsync(t->d_keys, bytes + v.keys, G * 8, hipMemcpyHostToDevice, S));
+    GHIP(hipMemcpyAsync(t->d_counts, bytes + v.counts, G * 8, hipMemcpyHostToDevice, S));
+    if (t->hashed) GHIP(hipMemcpyAsync(t->d_keys2, bytes + v.keys2, G * 8, hipMemcpyHostToDevice, S));
+  }
+  for (int c = 0; c < v.n_cols && t->hashed; ++c) {
+    StoreCol& sc = t->store[c];
+    sc.bytes = v.col_bytes[c];
+    GHIP(hipMalloc(&sc.values, std::max<int64_t>(8, sc.bytes)));
+    if (sc.bytes > 0) GHIP(hipMemcpyAsync(sc.values, bytes + v.col_values[c], sc.bytes, hipMemcpyHostToDevice, S));
+    if (v.col_offsets[c]) {
+      GHIP(hipMalloc(&sc.offsets, (G + 1) * 8));
+      GHIP(hipMemcpyAsync(sc.offsets, bytes + v.col_offsets[c], (G + 1) * 8, hipMemcpyHostToDevice, S));
+    }
+  }
+  t->has_store = t->hashed != 0;
+  GHIP(hipStreamSynchronize(S));
+  *out = guard.release();
+  return DQ_OK;
+}
+
+dq_status dq_freq_mutual_information(const dq_freq_table* t, int64_t num_rows, double* value, int32_t* defined) {
+  if (!t || !value || !defined) return set_error(DQ_E_INVALID, "dq_freq_mutual_information: NULL argument");
+  if (t->types.size() != 2) return set_error(DQ_E_STATE, "dq_freq_mutual_information: a table over %zu columns, not 2", t->types.size());
+  if (!t->has_store)
+    return set_error(DQ_E_STATE, "dq_freq_mutual_information: the table does not own its values (dq_freq_materialize it first)");
+  *defined = 0;
+  *value = 0.0;
+  const int64_t G = t->n_groups;
+  if (G == 0) return DQ_OK;  // sum over an empty join is NULL -> metricFromEmpty
+  GHIP(hipSetDevice(t->device));
+  std::lock_guard<std::mutex> lock(g_arena_mu);
+  const int D = t->device;
+  const hipStream_t S = t->stream;
+  DevBuf rep(D, 34), xk(D, 35), yk(D, 36), d_store(D, 60);
+  for (DevBuf* b : {&rep, &xk, &yk})
+    if (dq_status s = b->alloc(G * 8)) return s;
+  if (dq_status s = d_store.alloc(sizeof(GroupCols))) return s;
+  const GroupCols st = store_cols(t);
+  GHIP(hipMemcpyAsync(d_store.p, &st, sizeof(st), hipMemcpyHostToDevice, S));
+  GHIP(hipStreamSynchronize(S));
+  // group g is row g of the store: its row id and its index are both g
+  hipLaunchKernelGGL(iota_u64, dim3(grid_for(G)), dim3(256), 0, S, rep.as<uint64_t>(), G);
+  GHIP(hipGetLastError());
+  hipLaunchKernelGGL(store_col_keys, dim3(grid_for(G)), dim3(256), 0, S, st, G, xk.as<uint64_t>(), yk.as<uint64_t>());
+  GHIP(hipGetLastError());
+  const MiRequest mi{(double)num_rows, value, defined};
+  return mi_from_groups(D, S, G, t->d_counts, rep.as<uint64_t>(), xk.as<uint64_t>(), yk.as<uint64_t>(), rep.as<uint64_t>(),
+                        d_store.as<GroupCols>(), mi);
+}
+
+dq_status dq_freq_take_values(const dq_freq_table* t, const uint64_t* keys, int32_t n, int32_t col, void* values,
+                              int64_t values_cap, int64_t* offsets, int64_t* values_bytes) {
+  if (!t || n < 0 || !values_bytes || (n > 0 && !keys) || col < 0 || col >= (int)t->types.size())
+    return set_error(DQ_E_INVALID, "dq_freq_take_values: bad arguments");
+  if (!t->has_store) return set_error(DQ_E_STATE, "dq_freq_take_values: the table does not own its values");
+  const int es = dq_freq_elem_size(t->types[col]);
+  if (es == 0 && !offsets) return set_error(DQ_E_INVALID, "dq_freq_take_values: a string column needs offsets[n + 1]");
+  GHIP(hipSetDevice(t->device));
+  std::lock_guard<std::mutex> lock(g_arena_mu);
+  const int D = t->device;
+  const hipStream_t S = t->stream;
+  DevBuf want(D, 65), idx(D, 66), missing(D, 64), d_store(D, 60);
+  for (DevBuf* b : {&want, &idx})
+    if (dq_status s = b->alloc(std::max(1, n) * 8)) return s;
+  if (dq_status s = missing.alloc(8)) return s;
+  if (dq_status s = d_store.alloc(sizeof(GroupCols))) return s;
+  const GroupCols st = store_cols(t);
+  GHIP(hipMemcpyAsync(d_store.p, &st, sizeof(st), hipMemcpyHostToDevice, S));
+  if (n > 0) {
+    GHIP(hipMemcpyAsync(want.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, S));
+    GHIP(hipMemsetAsync(missing.p, 0, 8, S));
+    hipLaunchKernelGGL(find_groups, dim3((n + 255) / 256), dim3(256), 0, S, want.as<uint64_t>(), n, t->d_keys, t->n_groups,
+                       idx.as<uint64_t>(), missing.as<int32_t>());
+    GHIP(hipGetLastError());
+    int32_t miss = 0;
+    GHIP(hipMemcpyAsync(&miss, missing.p, 4, hipMemcpyDeviceToHost, S));
+    GHIP(hipStreamSynchronize(S));
+    if (miss) return set_error(DQ_E_INVALID, "dq_freq_take_values: a key that is not a group of the table");
+  }
+  GHIP(hipStreamSynchronize(S));
+  StoreCol got;
+  if (dq_status s = gather_column(D, S, d_store.as<GroupCols>(), idx.as<uint64_t>(), n, col, t->types[col], &got)) return s;
+  *values_bytes = got.bytes;
+  if (got.offsets) GHIP(hipMemcpyAsync(offsets, got.offsets, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, S));
+  if (values && values_cap >= got.bytes && got.bytes > 0)
+    GHIP(hipMemcpyAsync(values, got.values, got.bytes, hipMemcpyDeviceToHost, S));
+  GHIP(hipStreamSynchronize(S));
   return DQ_OK;
 }
 

@@ -117,6 +117,60 @@ class FreqTable:
                                      counts.ctypes.data_as(ctypes.c_void_p), max(1, n)))
         return keys[:n], counts[:n]
 
+    def self_contained(self) -> bool:
+        """True when the table owns its groups' values (an unhashed table's keys are its values; a hashed one after
+        materialize / from_bytes / a merge of two such tables)."""
+        return bool(L.lib.dq_freq_self_contained(self.handle))
+
+    def to_bytes(self) -> bytes:
+        """dq_freq_to_bytes: the table's byte image (include/dqscan.h); DQ_E_STATE unless self-contained."""
+        n = L.lib.dq_freq_to_bytes(self.handle, None, 0)
+        if n < 0:
+            L.check(int(n))
+        buf = (ctypes.c_uint8 * max(1, n))()
+        n2 = L.lib.dq_freq_to_bytes(self.handle, buf, n)
+        if n2 < 0:
+            L.check(int(n2))
+        return bytes(buf)[:n]
+
+    @staticmethod
+    def from_bytes(data: bytes) -> "FreqTable":
+        """dq_freq_from_bytes on the current torch device and stream (the image is checked on the host first)."""
+        import torch
+
+        h = ctypes.c_void_p()
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        L.check(L.lib.dq_freq_from_bytes(data, len(data), torch.cuda.current_device(), stream, ctypes.byref(h)))
+        img_cols = int.from_bytes(data[12:16], "little")
+        types = [int.from_bytes(data[16 + 4 * c:20 + 4 * c], "little") for c in range(img_cols)]
+        return FreqTable(h, types)
+
+    def take_values(self, keys, col: int = 0):
+        """The stored values of column col for the groups with these keys, in their order (dq_freq_take_values):
+        a list of bytes objects -- a string's bytes, or a fixed-width value's little-endian bytes."""
+        import numpy as np
+
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = len(keys)
+        kp = keys.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        offs = (ctypes.c_int64 * (n + 1))()
+        need = ctypes.c_int64()
+        L.check(L.lib.dq_freq_take_values(self.handle, kp, n, col, None, 0, offs, ctypes.byref(need)))
+        buf = (ctypes.c_uint8 * max(1, need.value))()
+        L.check(L.lib.dq_freq_take_values(self.handle, kp, n, col, buf, need.value, offs, ctypes.byref(need)))
+        raw = bytes(buf)[:need.value]
+        t = self.types[col]
+        if t in (L.TYPE_UTF8, L.TYPE_LARGE_UTF8):
+            return [raw[offs[i]:offs[i + 1]] for i in range(n)]
+        w = need.value // n if n else 0
+        return [raw[i * w:(i + 1) * w] for i in range(n)]
+
+    def mutual_information(self, num_rows: int) -> Optional[float]:
+        """dq_freq_mutual_information of a self-contained two-column table; None when it has no group."""
+        value, defined = ctypes.c_double(), ctypes.c_int32()
+        L.check(L.lib.dq_freq_mutual_information(self.handle, num_rows, ctypes.byref(value), ctypes.byref(defined)))
+        return value.value if defined.value else None
+
     def __del__(self):
         try:
             if self.handle:
@@ -124,6 +178,17 @@ class FreqTable:
                 self.handle = None
         except Exception:
             pass
+
+
+def _views(chunks, columns: Sequence[str]):
+    """The chunk-major column views and row counts dq_freq_build / dq_freq_materialize take."""
+    views = (L.ColumnView * max(1, len(chunks) * len(columns)))()
+    rows = (ctypes.c_int64 * max(1, len(chunks)))()
+    for k, t in enumerate(chunks):
+        rows[k] = t.num_rows
+        for c, name in enumerate(columns):
+            views[k * len(columns) + c] = t.columns[name].view()
+    return views, rows
 
 
 def build_frequencies(data, columns: Sequence[str]) -> "FrequenciesAndNumRows":
@@ -135,29 +200,45 @@ def build_frequencies(data, columns: Sequence[str]) -> "FrequenciesAndNumRows":
     chunks = _chunks(data)
     schema = {name: dt for name, dt, _ in chunks[0].schema}
     types = (ctypes.c_int32 * len(columns))(*[_gpu_type(schema[c]) for c in columns])
-    views = (L.ColumnView * max(1, len(chunks) * len(columns)))()
-    rows = (ctypes.c_int64 * max(1, len(chunks)))()
-    for k, t in enumerate(chunks):
-        rows[k] = t.num_rows
-        for c, name in enumerate(columns):
-            views[k * len(columns) + c] = t.columns[name].view()
+    views, rows = _views(chunks, columns)
     h = ctypes.c_void_p()
     dev = torch.cuda.current_device()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     L.check(L.lib.dq_freq_build(types, len(columns), views, rows, len(chunks), dev, stream, ctypes.byref(h)))
-    return FrequenciesAndNumRows(FreqTable(h, list(types)), sum(t.num_rows for t in chunks))
+    return FrequenciesAndNumRows(FreqTable(h, list(types)), sum(t.num_rows for t in chunks),
+                                 source=(chunks, list(columns)))
 
 
 class FrequenciesAndNumRows(State):
-    """GroupingAnalyzers.scala:118-138 (the frequencies live on the device)."""
+    """GroupingAnalyzers.scala:118-138 (the frequencies live on the device).
+
+    A state built from data over strings, decimals or several columns names its groups' values by row ids into the
+    tables it was built from, and remembers those tables: while an unmaterialised state lives, its input tables stay
+    alive.  materialize() copies the values into the table (dq_freq_materialize) once and drops that reference; sum
+    and HdfsStateProvider.persist materialise first, so merged, persisted and loaded states are self-contained."""
 
     OP = -1
 
-    def __init__(self, frequencies: FreqTable, numRows: int):
+    def __init__(self, frequencies: FreqTable, numRows: int, source=None):
         self.frequencies = frequencies
         self.numRows = int(numRows)
+        self._source = source  # (chunks, columns) the table was built from, until materialize()
+
+    def materialize(self) -> "FrequenciesAndNumRows":
+        src, self._source = self._source, None
+        if src is not None:
+            try:
+                chunks, columns = src
+                views, rows = _views(chunks, columns)
+                L.check(L.lib.dq_freq_materialize(self.frequencies.handle, views, rows, len(chunks)))
+            except Exception:
+                self._source = src
+                raise
+        return self
 
     def sum(self, other: "FrequenciesAndNumRows") -> "FrequenciesAndNumRows":
+        self.materialize()
+        other.materialize()
         return FrequenciesAndNumRows(self.frequencies.merged(other.frequencies), self.numRows + other.numRows)
 
     def __eq__(self, other):
@@ -169,7 +250,8 @@ class FrequenciesAndNumRows(State):
     __hash__ = None
 
     def _to_c(self):
-        raise TypeError("FrequenciesAndNumRows has no fixed-size dq_state (HdfsStateProvider stores it as parquet)")
+        raise TypeError("FrequenciesAndNumRows has no fixed-size dq_state (HdfsStateProvider stores the table's "
+                        "image: FreqTable.to_bytes)")
 
 
 class FrequencyBasedAnalyzer(Analyzer):
@@ -284,9 +366,10 @@ class Entropy(FrequencyBasedAnalyzer):  # Entropy.scala:26-44 (single column)
 
 class MutualInformation(FrequencyBasedAnalyzer):  # MutualInformation.scala:32-80
     """sum over the joint groups of (pxy/N) ln((pxy/N) / ((px/N)(py/N))), marginals summed from the joint
-    counts (rows with both values), N = numRows -- computed in one device pass (dq_mutual_information).
-    The joint frequencies are not materialised as a state here: aggregateWith / saveStatesWith of a
-    MutualInformation are reported as failures of that metric."""
+    counts (rows with both values), N = numRows.  calculate(data) alone is one device pass over the rows
+    (dq_mutual_information); with a loader or persister the state is the joint frequencies of the two columns
+    (build_frequencies, made self-contained) and the metric comes from it (dq_freq_mutual_information), as do
+    runOnAggregatedStates and loadStateAndComputeMetric."""
     name = "MutualInformation"
     direct = True
 
@@ -331,10 +414,18 @@ class MutualInformation(FrequencyBasedAnalyzer):  # MutualInformation.scala:32-8
             for cond in self.preconditions():
                 cond(data_schema(data))
             if aggregateWith is not None or saveStatesWith is not None:
-                raise NotImplementedError("incremental MutualInformation needs the joint frequencies as a state")
+                return self.calculateMetric(self.computeStateFrom(data), aggregateWith, saveStatesWith)
             return self.compute(data)
         except Exception as e:
             return self.toFailureMetric(e)
+
+    def computeMetricFrom(self, state: Optional[FrequenciesAndNumRows]) -> DoubleMetric:
+        if state is None:
+            return self._empty()
+        v = state.materialize().frequencies.mutual_information(state.numRows)
+        if v is None:
+            return self._empty()
+        return DoubleMetric(self.entity, self.name, self.instance, Success(v))
 
 
 def _java_double_to_string(d: float) -> str:
@@ -428,8 +519,17 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
         o = col.offsets[r * width:(r + 2) * width].cpu().numpy().view(np.int64 if width == 8 else np.int32)
         return bytes(col.values[int(o[0]):int(o[1])].cpu().numpy()).decode("utf-8", "replace")
 
+    def computeMetricFrom(self, state: Optional["FrequenciesAndNumRows"]):
+        """The metric from a state alone (runOnAggregatedStates, loadStateAndComputeMetric): a self-contained table
+        renders its bins from its own values."""
+        if state is None:
+            return self.toFailureMetric(EmptyStateException(
+                f"Empty state for analyzer {self}, all input values were NULL."))
+        return self.computeMetricFromState(state.materialize(), None)
+
     def computeMetricFromState(self, state: "FrequenciesAndNumRows", data):
         from .metrics import Distribution, DistributionValue, HistogramMetric
+        from .table import decimal_ps
 
         n = self.maxDetailBins
         keys = (ctypes.c_uint64 * max(1, n))()
@@ -440,7 +540,15 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
         t0 = state.frequencies.types[0]
         dtype = ({v: k for k, v in _TYPES.items()}.get(t0) or
                  f"decimal({(t0 >> 8) & 0xFF},{(t0 >> 16) & 0xFF})")  # (a DQ_DECIMAL128 code carries p, s)
-        bins = [(self._render(data, dtype, keys[i], reps[i]), int(counts[i])) for i in range(got.value)]
+        ps = decimal_ps(dtype)
+        if (dtype in ("utf8", "large_utf8") or ps) and state.frequencies.self_contained():
+            # strings / decimals of a table that owns its values: the selected groups' values from its store
+            vals = state.frequencies.take_values([keys[i] for i in range(got.value)], 0)
+            names = [_java_decimal_to_string(int.from_bytes(v, "little", signed=True), ps[1]) if ps
+                     else v.decode("utf-8", "replace") for v in vals]
+            bins = [(names[i], int(counts[i])) for i in range(got.value)]
+        else:  # fixed-width keys are the values; an unmaterialised table reads its representative rows
+            bins = [(self._render(data, dtype, keys[i], reps[i]), int(counts[i])) for i in range(got.value)]
         summary = state.frequencies.summary(state.numRows)
         nulls = state.numRows - summary.num_values
         bin_count = summary.num_groups
@@ -467,6 +575,8 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
 
                 raise UnsupportedOnGpuPathException(f"{self}: a binning UDF runs in Spark, not on the GPU path")
             state = build_frequencies(data, [self.column])
+            if aggregateWith is not None or saveStatesWith is not None:
+                state.materialize()  # once, before the merge and the first persist
             if aggregateWith is not None:
                 prev = aggregateWith.load(self)
                 if prev is not None:

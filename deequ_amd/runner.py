@@ -283,6 +283,11 @@ class AnalysisRunner:
         except Exception as e:
             return AnalyzerContext({a: a.toFailureMetric(e) for a in analyzers})
         metrics = {}
+        if saveStatesWith is not None:
+            try:
+                state.materialize()  # once, before the first persist: a persisted state owns its values
+            except Exception as e:
+                return AnalyzerContext({a: a.toFailureMetric(e) for a in analyzers})
         for a in analyzers:
             try:
                 if saveStatesWith is not None:

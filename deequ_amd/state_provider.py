@@ -3,7 +3,9 @@
 InMemoryStateProvider keeps states keyed by analyzer (case-class equality).  HdfsStateProvider
 writes the reference's binary images -- `<prefix>-<MurmurHash3.stringHash(analyzer.toString, 42)>.bin`,
 Java DataOutputStream big-endian -- through dq_state_to_bytes / dq_state_from_bytes /
-dq_state_identifier of libdqscan.so, on a local (or mounted) file system.
+dq_state_identifier of libdqscan.so, on a local (or mounted) file system.  The grouping analyzers' states are
+`<prefix>-<id>-frequencies.dqf` (the frequency table's own byte image, dq_freq_to_bytes) and
+`<prefix>-<id>-num_rows.bin` (the reference's file: one big-endian long).
 """
 from __future__ import annotations
 
@@ -47,6 +49,13 @@ def identifier(analyzer) -> str:
     return str(L.lib.dq_state_identifier(str(analyzer).encode("utf-8")))
 
 
+def _has_frequency_state(analyzer) -> bool:
+    """A FrequencyBasedAnalyzer or a Histogram: its state is FrequenciesAndNumRows."""
+    from .grouping import FrequencyBasedAnalyzer, Histogram
+
+    return isinstance(analyzer, (FrequencyBasedAnalyzer, Histogram))
+
+
 class HdfsStateProvider(StateLoader, StatePersister):
     def __init__(self, locationPrefix: str, allowOverwrite: bool = False):
         self.locationPrefix = locationPrefix
@@ -55,9 +64,42 @@ class HdfsStateProvider(StateLoader, StatePersister):
     def _path(self, analyzer) -> str:
         return f"{self.locationPrefix}-{identifier(analyzer)}.bin"
 
+    def _frequency_paths(self, analyzer):
+        """A grouping analyzer's two files (StateProvider.scala:211-223): the frequencies -- here the table's byte
+        image (dq_freq_to_bytes), where the reference writes parquet -- and numRows as an 8-byte big-endian long."""
+        base = f"{self.locationPrefix}-{identifier(analyzer)}"
+        return f"{base}-frequencies.dqf", f"{base}-num_rows.bin"
+
+    def _persist_frequencies(self, analyzer, state):
+        image = state.materialize().frequencies.to_bytes()
+        paths = self._frequency_paths(analyzer)
+        for path in paths:
+            if os.path.exists(path) and not self.allowOverwrite:
+                raise FileExistsError(f"File {path} already exists!")
+        with open(paths[0], "wb") as f:
+            f.write(image)
+        with open(paths[1], "wb") as f:
+            f.write(int(state.numRows).to_bytes(8, "big", signed=True))
+
+    def _load_frequencies(self, analyzer):
+        from .grouping import FreqTable, FrequenciesAndNumRows
+
+        paths = self._frequency_paths(analyzer)
+        if not (os.path.exists(paths[0]) and os.path.exists(paths[1])):
+            return None
+        with open(paths[0], "rb") as f:
+            image = f.read()
+        with open(paths[1], "rb") as f:
+            num_rows = f.read()
+        if len(num_rows) != 8:
+            raise L.DQError(L.DQ_E_STATE, f"{paths[1]}: {len(num_rows)} bytes, expected an 8-byte long")
+        return FrequenciesAndNumRows(FreqTable.from_bytes(image), int.from_bytes(num_rows, "big", signed=True))
+
     def persist(self, analyzer, state):
         from .quantiles import ApproxQuantileState
 
+        if _has_frequency_state(analyzer):  # StateProvider.scala:108-109
+            return self._persist_frequencies(analyzer, state)
         if isinstance(state, ApproxQuantileState):  # ApproximatePercentile.serializer (StateProvider.scala:126-129)
             buf = state.percentileDigest.serialize()
         else:
@@ -74,6 +116,8 @@ class HdfsStateProvider(StateLoader, StatePersister):
             f.write(bytes(buf))
 
     def load(self, analyzer):
+        if _has_frequency_state(analyzer):
+            return self._load_frequencies(analyzer)
         path = self._path(analyzer)
         if not os.path.exists(path):
             return None

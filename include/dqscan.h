@@ -39,7 +39,9 @@ extern "C" {
                              5: column types F32 / I16 / I8 / BOOL / DATE32 / TIMESTAMP (scan, predicates, Arrow import);
                              6: DECIMAL128 (type codes carry precision / scale, dq_state Sum / Mean decimal partials);
                                 dq_cast_utf8, the dq_cat_hist_* entry points, the dq_schema_* / dq_take_* / dq_split_*
-                                entry points and dq_pred_jit_drain are additions under 6 (nothing existing changed its layout or meaning) */
+                                entry points and dq_pred_jit_drain are additions under 6 (nothing existing changed its layout or meaning);
+                                so are dq_freq_materialize / _self_contained / _to_bytes / _from_bytes / _take_values /
+                                _mutual_information (self-contained frequency tables) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -422,6 +424,43 @@ dq_status dq_freq_summarize(const dq_freq_table* t, int64_t num_rows, dq_freq_su
 int64_t dq_freq_num_groups(const dq_freq_table* t);
 dq_status dq_freq_export(const dq_freq_table* t, uint64_t* keys, int64_t* counts, int64_t cap);
 void dq_freq_destroy(dq_freq_table* t);
+/* Self-contained frequency tables (the state of the grouping analyzers as Deequ's State / StatePersister /
+ * StateLoader model needs it).  A hashed table built from data names every group's value only by a row id into the
+ * caller's chunks.  dq_freq_materialize gathers those representative tuples into a store the table owns: per grouping
+ * column exactly n_groups entries in group order and no validity (groups hold no NULL) -- a dense array for
+ * fixed-width types (16 bytes per DECIMAL128, one byte per BOOL), int64 offsets[n_groups + 1] plus the bytes for
+ * UTF8 / LARGE_UTF8.  cols / chunk_rows / n_chunks: the views the table was built from.  A second call and a call on
+ * an unhashed table (its keys are its values) do nothing; a hashed table with groups but no representative rows (a
+ * merge of tables without values) is DQ_E_STATE; chunks that do not cover the stored row ids are DQ_E_INVALID.
+ * dq_freq_self_contained: 1 for an unhashed table or one with a store.
+ * dq_freq_merge of two self-contained tables gives a self-contained table (each group's tuple from either input) and
+ * compares groups of equal first hash value by value (distinct tuples: DQ_E_UNSUPPORTED); with either input not
+ * self-contained the second hash decides and the output carries no values.
+ * dq_freq_to_bytes / dq_freq_from_bytes: the table's byte image, the library's own format (returns the length, or a
+ * negative dq_status; writes nothing when out is NULL or cap too small).  A table that is not self-contained is
+ * DQ_E_STATE.  dq_freq_from_bytes checks the whole image on the host before it allocates or copies (wrong magic /
+ * version / byte order, truncation, sizes beyond n, n_groups >= 2^31, keys not strictly ascending, a count < 1, counts
+ * not adding up to n_values, bad string offsets, an unknown type code: DQ_E_STATE with a message) and rebuilds the
+ * table on `device` / `hip_stream`.  The image, every integer little-endian:
+ *   u8[4] "DQFT"; u32 version = 1; u32 0x01020304 (byte-order marker); i32 n_cols;
+ *   i32 types[n_cols] (a DECIMAL128 code carries precision and scale), one zero i32 when n_cols is odd;
+ *   i32 hashed; i32 0; i64 n_groups; i64 n_values;
+ *   u64 keys[n_groups]; i64 counts[n_groups]; hashed tables: u64 keys2[n_groups];
+ *   hashed tables, per column: the n_groups values zero-padded to 8 bytes, or for strings i64 n_bytes,
+ *   i64 offsets[n_groups + 1], the n_bytes bytes zero-padded to 8 bytes.
+ * dq_freq_take_values: the stored values of column `col` for the groups with the given keys (e.g. dq_freq_top's), in
+ * that order: *values_bytes = their length; copied to `values` when values_cap holds them (call with values = NULL
+ * for the size); a string column also fills offsets[n + 1].  A key that is no group: DQ_E_INVALID.
+ * dq_freq_mutual_information: MutualInformation of a self-contained two-column table, marginals and sum as
+ * dq_mutual_information takes them, N = num_rows; *defined = 0 for an empty table. */
+dq_status dq_freq_materialize(dq_freq_table* t, const dq_column_view* cols, const int64_t* chunk_rows,
+                              int32_t n_chunks);
+int32_t dq_freq_self_contained(const dq_freq_table* t);
+int64_t dq_freq_to_bytes(const dq_freq_table* t, uint8_t* out, int64_t cap);
+dq_status dq_freq_from_bytes(const uint8_t* bytes, int64_t n, int32_t device, void* hip_stream, dq_freq_table** out);
+dq_status dq_freq_take_values(const dq_freq_table* t, const uint64_t* keys, int32_t n, int32_t col, void* values,
+                              int64_t values_cap, int64_t* offsets, int64_t* values_bytes);
+dq_status dq_freq_mutual_information(const dq_freq_table* t, int64_t num_rows, double* value, int32_t* defined);
 /* ColumnProfiler.computeHistograms (profiles/ColumnProfiler.scala:518-565): the counts of every value of n_cols
  * low-cardinality columns in one pass over the data -- what one dq_freq_build per column gives, without its sort,
  * for columns the profiler's first pass found to hold few distinct values.  types: DQ_TYPE_UTF8 / LARGE_UTF8 / BOOL
