@@ -7,6 +7,13 @@ is the host-side mirror of the reference's analyzer / state / runner API over th
 from ._lib import DQError, lib  # noqa: F401  (fails loudly if libdqscan.so is missing)
 from .checks import (Check, CheckLevel, CheckStatus, ConstrainableDataTypes, ConstraintStatus,  # noqa: F401
                      VerificationResult, VerificationSuite)
+from .checks import AnomalyCheckConfig, getAnomalyCheck  # noqa: F401
+from .anomaly import (Anomaly, AnomalyDetectionStrategy, AnomalyDetector, BatchNormalStrategy, DataPoint,  # noqa: F401
+                      DetectionResult, HistoryUtils, HoltWinters, OnlineNormalStrategy, RateOfChangeStrategy,
+                      SimpleThresholdStrategy)
+from .repository import (AnalysisResult, AnalysisResultSerde, FileSystemMetricsRepository,  # noqa: F401
+                         InMemoryMetricsRepository, MetricsRepository, MetricsRepositoryMultipleResultsLoader,
+                         ResultKey)
 from .analyzers import (ApproxCountDistinct, Completeness, Compliance, Correlation, DataType,  # noqa: F401
                         DataTypeInstances, Maximum, Mean, Minimum, PatternMatch, Patterns, Size, StandardDeviation,
                         Sum)
@@ -17,7 +24,7 @@ from .metrics import (DoubleMetric, Distribution, DistributionValue, Entity, His
 from .profiles import (ColumnProfiler, ColumnProfiles, NumericColumnProfile, StandardColumnProfile,  # noqa: F401
                        compute_histograms)
 from .quantiles import ApproxQuantile, ApproxQuantiles  # noqa: F401
-from .runner import AnalysisRunner, AnalyzerContext  # noqa: F401
+from .runner import AnalysisRunner, AnalyzerContext, ReusingNotPossibleResultsMissingException  # noqa: F401
 from .schema import (RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator)  # noqa: F401
 from .split import random_split  # noqa: F401
 from .suggestions import (ConstraintSuggestion, ConstraintSuggestionResult, ConstraintSuggestionRunner,  # noqa: F401

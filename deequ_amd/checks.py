@@ -20,6 +20,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
 from .analyzers import DataType, DataTypeInstances
 from .grouping import (Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
+from .quantiles import ApproxQuantile
 from .runner import AnalysisRunner, AnalyzerContext
 
 
@@ -147,6 +148,36 @@ def data_type_constraint(column, dataType, assertion=_is_one, hint=None) -> Anal
     """Constraint.dataTypeConstraint (Constraint.scala:548-571): the one factory that returns the bare
     AnalysisBasedConstraint, so its name is that case class's toString."""
     return AnalysisBasedConstraint(DataType(column), assertion, data_type_value_picker(dataType), hint)
+
+
+def is_newest_point_non_anomalous(metricsRepository, anomalyDetectionStrategy, analyzer, withTagValues,
+                                  afterDate: Optional[int], beforeDate: Optional[int],
+                                  currentMetricValue: float) -> bool:
+    """Check.isNewestPointNonAnomalous of the companion object (Check.scala:926-983): the history of the analyzer's
+    metric from the repository (tag filter, before and after both inclusive), the current value appended one tick
+    after the newest stored result, and the strategy asked about that last point only."""
+    from .anomaly import AnomalyDetector, DataPoint, HistoryUtils
+
+    loader = metricsRepository.load().withTagValues(withTagValues)
+    if beforeDate is not None:
+        loader = loader.before(beforeDate)
+    if afterDate is not None:
+        loader = loader.after(afterDate)
+    results = loader.forAnalyzers([analyzer]).get()
+    if not results:
+        raise ValueError("requirement failed: There have to be previous results in the MetricsRepository!")
+    # results of one dateTime are ordered by their tag values first (the sort is stable)
+    historical = []
+    for r in sorted(results, key=lambda r: list(r.resultKey.tags.values())):
+        metrics = list(r.analyzerContext.metricMap.values())
+        historical.append((r.resultKey.dataSetDate, metrics[0] if metrics else None))
+    testDateTime = max(r.resultKey.dataSetDate for r in results) + 1
+    if testDateTime == 2 ** 63 - 1:
+        raise ValueError("requirement failed: Test DateTime cannot be Long.MaxValue, otherwise the"
+                         "Anomaly Detection, which works with an open upper interval bound, won't test anything")
+    detected = AnomalyDetector(anomalyDetectionStrategy).isNewPointAnomalous(
+        HistoryUtils.extractMetricValues(historical), DataPoint(testDateTime, currentMetricValue))
+    return not detected.anomalies
 
 
 class CheckResult:  # Check.scala:39-42
@@ -289,6 +320,41 @@ class Check:  # Check.scala:59-902
     def hasDataType(self, column, dataType, assertion=_is_one, hint=None):  # Check.scala:653-661
         return self.addConstraint(data_type_constraint(column, dataType, assertion, hint))
 
+    def hasApproxQuantile(self, column, quantile, assertion, hint=None):  # Check.scala:391-398
+        return self.addConstraint(_named(ApproxQuantile(column, quantile), assertion, "ApproxQuantileConstraint",
+                                         None, hint))
+
+    # the pattern checks of Check.scala:581-642; a pattern outside the GPU regex subset (the credit card and social
+    # security number patterns) gives the failure metric PatternMatch gives for it
+    def containsCreditCardNumber(self, column, assertion=_is_one, hint=None):
+        from .analyzers import Patterns
+
+        return self.hasPattern(column, Patterns.CREDITCARD, assertion, f"containsCreditCardNumber({column})", hint)
+
+    def containsEmail(self, column, assertion=_is_one, hint=None):
+        from .analyzers import Patterns
+
+        return self.hasPattern(column, Patterns.EMAIL, assertion, f"containsEmail({column})", hint)
+
+    def containsURL(self, column, assertion=_is_one, hint=None):
+        from .analyzers import Patterns
+
+        return self.hasPattern(column, Patterns.URL, assertion, f"containsURL({column})", hint)
+
+    def containsSocialSecurityNumber(self, column, assertion=_is_one, hint=None):
+        from .analyzers import Patterns
+
+        return self.hasPattern(column, Patterns.SOCIAL_SECURITY_NUMBER_US, assertion,
+                               f"containsSocialSecurityNumber({column})", hint)
+
+    def isNewestPointNonAnomalous(self, metricsRepository, anomalyDetectionStrategy, analyzer, withTagValues=None,
+                                  afterDate=None, beforeDate=None, hint=None):  # Check.scala:322-342
+        def assertion(currentMetricValue):
+            return is_newest_point_non_anomalous(metricsRepository, anomalyDetectionStrategy, analyzer,
+                                                 dict(withTagValues or {}), afterDate, beforeDate, currentMetricValue)
+        # Constraint.anomalyConstraint (Constraint.scala:180-190)
+        return self.addConstraint(_named(analyzer, assertion, "AnomalyConstraint", None, hint))
+
     # ---- evaluation --------------------------------------------------------------------------------
     def evaluate(self, context: AnalyzerContext) -> CheckResult:  # Check.scala:878-890
         results = [c.evaluate(context.metricMap) for c in self.constraints]
@@ -330,16 +396,42 @@ class VerificationSuite:  # VerificationSuite.scala:42-282
 
     @staticmethod
     def doVerificationRun(data, checks: Sequence[Check], requiredAnalyzers: Sequence[Analyzer] = (),
-                          aggregateWith=None, saveStatesWith=None) -> VerificationResult:
+                          aggregateWith=None, saveStatesWith=None, metricsRepository=None,
+                          reuseExistingResultsForKey=None, failIfResultsForReusingMissing: bool = False,
+                          saveOrAppendResultsWithKey=None) -> VerificationResult:
         analyzers = list(requiredAnalyzers) + [a for c in checks for a in c.requiredAnalyzers()]
-        context = AnalysisRunner.doAnalysisRun(data, analyzers, aggregateWith, saveStatesWith)
-        return VerificationSuite._evaluate(checks, context)
+        # the analysis run reuses but does not save (VerificationSuite.scala:121-130): the checks, the anomaly checks
+        # among them, are evaluated against the repository as it was, and the metrics are stored after that (:132-139)
+        context = AnalysisRunner.doAnalysisRun(data, analyzers, aggregateWith, saveStatesWith, metricsRepository,
+                                               reuseExistingResultsForKey, failIfResultsForReusingMissing, None)
+        result = VerificationSuite._evaluate(checks, context)
+        if metricsRepository is not None and saveOrAppendResultsWithKey is not None:
+            from .repository import save_or_append_result
+
+            save_or_append_result(AnalyzerContext(result.metrics), metricsRepository, saveOrAppendResultsWithKey)
+        return result
 
     @staticmethod
     def _evaluate(checks, context: AnalyzerContext) -> VerificationResult:  # VerificationSuite.scala:263-281
         results = {c: c.evaluate(context) for c in checks}
         status = max((r.status for r in results.values()), default=CheckStatus.Success)
         return VerificationResult(CheckStatus(status), results, context.metricMap)
+
+
+class AnomalyCheckConfig:  # VerificationRunBuilder.scala:303-308
+    def __init__(self, level: CheckLevel, description: str, withTagValues: Optional[Dict[str, str]] = None,
+                 afterDate: Optional[int] = None, beforeDate: Optional[int] = None):
+        self.level, self.description = level, description
+        self.withTagValues: Dict[str, str] = dict(withTagValues or {})
+        self.afterDate, self.beforeDate = afterDate, beforeDate
+
+
+def getAnomalyCheck(metricsRepository, anomalyDetectionStrategy, analyzer,
+                    anomalyCheckConfig: AnomalyCheckConfig) -> Check:
+    """VerificationRunBuilderHelper.getAnomalyCheck (VerificationRunBuilder.scala:269-285)."""
+    return Check(anomalyCheckConfig.level, anomalyCheckConfig.description).isNewestPointNonAnomalous(
+        metricsRepository, anomalyDetectionStrategy, analyzer, anomalyCheckConfig.withTagValues,
+        anomalyCheckConfig.afterDate, anomalyCheckConfig.beforeDate)
 
 
 class VerificationRunBuilder:  # VerificationRunBuilder.scala:28-149
@@ -349,6 +441,10 @@ class VerificationRunBuilder:  # VerificationRunBuilder.scala:28-149
         self.required: List[Analyzer] = []
         self._aggregateWith = None
         self._saveStatesWith = None
+        self._metricsRepository = None
+        self._reuseExistingResultsKey = None
+        self._failIfResultsForReusingMissing = False
+        self._saveOrAppendResultsKey = None
 
     def addCheck(self, check: Check) -> "VerificationRunBuilder":
         self.checks.append(check)
@@ -374,6 +470,32 @@ class VerificationRunBuilder:  # VerificationRunBuilder.scala:28-149
         self._saveStatesWith = persister
         return self
 
+    # VerificationRunBuilderWithRepository (VerificationRunBuilder.scala:151-211): one builder class here
+    def useRepository(self, metricsRepository) -> "VerificationRunBuilder":
+        self._metricsRepository = metricsRepository
+        return self
+
+    def reuseExistingResultsForKey(self, resultKey, failIfResultsMissing: bool = False) -> "VerificationRunBuilder":
+        self._reuseExistingResultsKey = resultKey
+        self._failIfResultsForReusingMissing = failIfResultsMissing
+        return self
+
+    def saveOrAppendResult(self, resultKey) -> "VerificationRunBuilder":
+        self._saveOrAppendResultsKey = resultKey
+        return self
+
+    def addAnomalyCheck(self, anomalyDetectionStrategy, analyzer,
+                        anomalyCheckConfig: Optional[AnomalyCheckConfig] = None) -> "VerificationRunBuilder":
+        """A check that the analyzer's new metric is no anomaly against its history in the repository (:194-210);
+        without a config: level Warning, description "Anomaly check for <analyzer>"."""
+        if self._metricsRepository is None:
+            raise ValueError("addAnomalyCheck needs a metrics repository: call useRepository first")
+        config = anomalyCheckConfig or AnomalyCheckConfig(CheckLevel.Warning, f"Anomaly check for {analyzer}")
+        self.checks.append(getAnomalyCheck(self._metricsRepository, anomalyDetectionStrategy, analyzer, config))
+        return self
+
     def run(self) -> VerificationResult:
         return VerificationSuite.doVerificationRun(self.data, self.checks, self.required, self._aggregateWith,
-                                                   self._saveStatesWith)
+                                                   self._saveStatesWith, self._metricsRepository,
+                                                   self._reuseExistingResultsKey, self._failIfResultsForReusingMissing,
+                                                   self._saveOrAppendResultsKey)

@@ -237,16 +237,45 @@ class AnalyzerContext:
         return json.dumps(rows)
 
 
+class ReusingNotPossibleResultsMissingException(RuntimeError):  # AnalysisRunner.scala:538-539
+    pass
+
+
 class AnalysisRunner:
     @staticmethod
     def onData(data) -> "AnalysisRunBuilder":
         return AnalysisRunBuilder(data)
 
     @staticmethod
-    def doAnalysisRun(data, analyzers: Sequence[Analyzer], aggregateWith=None, saveStatesWith=None) -> AnalyzerContext:
+    def doAnalysisRun(data, analyzers: Sequence[Analyzer], aggregateWith=None, saveStatesWith=None,
+                      metricsRepository=None, reuseExistingResultsForKey=None,
+                      failIfResultsForReusingMissing: bool = False, saveOrAppendResultsWithKey=None) -> AnalyzerContext:
         if not analyzers:
             return AnalyzerContext.empty()
         all_analyzers = list(dict.fromkeys(analyzers))  # case-class equality dedup, order kept
+        # AnalysisRunner.scala:116-135: a metric stored under the reuse key is not computed again; its analyzer
+        # leaves the run here, before the preconditions and before any plan is built
+        previous = AnalyzerContext.empty()
+        if metricsRepository is not None and reuseExistingResultsForKey is not None:
+            previous = metricsRepository.loadByKey(reuseExistingResultsForKey) or AnalyzerContext.empty()
+        all_analyzers = [a for a in all_analyzers if a not in previous.metricMap]
+        if failIfResultsForReusingMissing and all_analyzers:
+            raise ReusingNotPossibleResultsMissingException(
+                "Could not find all necessary results in the MetricsRepository, the calculation of "
+                f"the metrics for these analyzers would be needed: {', '.join(str(a) for a in all_analyzers)}")
+        result = previous + AnalysisRunner._run_analyzers(data, all_analyzers, aggregateWith, saveStatesWith)
+        if metricsRepository is not None and saveOrAppendResultsWithKey is not None:
+            from .repository import save_or_append_result
+
+            save_or_append_result(result, metricsRepository, saveOrAppendResultsWithKey)  # :185-188
+        return result
+
+    @staticmethod
+    def _run_analyzers(data, all_analyzers: Sequence[Analyzer], aggregateWith=None,
+                       saveStatesWith=None) -> AnalyzerContext:
+        """doAnalysisRun from the preconditions on (AnalysisRunner.scala:137-183)."""
+        if not all_analyzers:
+            return AnalyzerContext.empty()
         schema = data_schema(data)
         passed, failures = [], {}
         for a in all_analyzers:
@@ -331,7 +360,8 @@ class AnalysisRunner:
 
     @staticmethod
     def runOnAggregatedStates(schema, analyzers: Sequence[Analyzer], stateLoaders: Sequence,
-                              saveStatesWith=None) -> AnalyzerContext:
+                              saveStatesWith=None, metricsRepository=None,
+                              saveOrAppendResultsWithKey=None) -> AnalyzerContext:
         """AnalysisRunner.scala:375-446: merge persisted states without touching data."""
         from .state_provider import InMemoryStateProvider
 
@@ -357,7 +387,12 @@ class AnalysisRunner:
                 metrics[a] = m
             except Exception as e:
                 metrics[a] = a.toFailureMetric(e)
-        return AnalyzerContext(metrics)
+        results = AnalyzerContext(metrics)
+        if metricsRepository is not None and saveOrAppendResultsWithKey is not None:  # AnalysisRunner.scala:443
+            from .repository import save_or_append_result
+
+            save_or_append_result(results, metricsRepository, saveOrAppendResultsWithKey)
+        return results
 
 
 class AnalysisRunBuilder:
@@ -366,6 +401,10 @@ class AnalysisRunBuilder:
         self.analyzers: List[Analyzer] = []
         self._aggregateWith = None
         self._saveStatesWith = None
+        self._metricsRepository = None
+        self._reuseExistingResultsKey = None
+        self._failIfResultsForReusingMissing = False
+        self._saveOrAppendResultsKey = None
 
     def addAnalyzer(self, a: Analyzer) -> "AnalysisRunBuilder":
         self.analyzers.append(a)
@@ -383,5 +422,22 @@ class AnalysisRunBuilder:
         self._saveStatesWith = persister
         return self
 
+    # AnalysisRunBuilderWithRepository (AnalysisRunBuilder.scala:83-153): one builder class here, the options of the
+    # repository take effect once useRepository has set one
+    def useRepository(self, metricsRepository) -> "AnalysisRunBuilder":
+        self._metricsRepository = metricsRepository
+        return self
+
+    def reuseExistingResultsForKey(self, resultKey, failIfResultsMissing: bool = False) -> "AnalysisRunBuilder":
+        self._reuseExistingResultsKey = resultKey
+        self._failIfResultsForReusingMissing = failIfResultsMissing
+        return self
+
+    def saveOrAppendResult(self, resultKey) -> "AnalysisRunBuilder":
+        self._saveOrAppendResultsKey = resultKey
+        return self
+
     def run(self) -> AnalyzerContext:
-        return AnalysisRunner.doAnalysisRun(self.data, self.analyzers, self._aggregateWith, self._saveStatesWith)
+        return AnalysisRunner.doAnalysisRun(self.data, self.analyzers, self._aggregateWith, self._saveStatesWith,
+                                            self._metricsRepository, self._reuseExistingResultsKey,
+                                            self._failIfResultsForReusingMissing, self._saveOrAppendResultsKey)
