@@ -27,7 +27,7 @@
 #include <locale.h>
 
 #include "dq_cast.h"
-#include "dq_internal.h"
+#include "dq_hip_host.h"
 
 #define DQ_DEC_TABLE static __constant__ const
 #include "dq_dec_tables.inc"
@@ -146,21 +146,6 @@ __global__ void dq_cast_hard_scatter(const int64_t* __restrict__ rows, const uin
   if (i < count) out_values[rows[i]] = vals[i];
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-#define CHIP(call)                                                                                         \
-  do {                                                                                                     \
-    const hipError_t e_ = (call);                                                                          \
-    if (e_ != hipSuccess)                                                                                  \
-      return set_error(e_ == hipErrorOutOfMemory ? DQ_E_OOM : DQ_E_HIP, "dq_cast_utf8: %s failed: %s", #call, \
-                       hipGetErrorString(e_));                                                             \
-  } while (0)
-
 // the exact conversion of one hard value: Java's grammar first (dq_cast.h), then strtod on the delimited text
 bool hard_to_double(const uint8_t* p, int64_t n, locale_t c_loc, uint64_t& bits) {
   static const DecTab& t = dec_host_tab();
@@ -207,19 +192,20 @@ extern "C" dq_status dq_cast_utf8(int32_t src_type, const dq_column_view* src, i
   if (src_type == DQ_TYPE_UTF8 && n_rows >= INT32_MAX) return set_error(DQ_E_INVALID, "dq_cast_utf8: UTF8 chunk of %lld rows", (long long)n_rows);
   const bool large = src_type == DQ_TYPE_LARGE_UTF8, f64 = to_type == DQ_TYPE_F64;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  CHIP(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
 
   int64_t hard_cap = f64 ? kHardCapDefault : 0;
   if (const char* e = std::getenv("DQ_CAST_HARD_CAP"))  // the first list's capacity (tests force the rerun with it)
     if (f64 && std::atoll(e) > 0) hard_cap = std::atoll(e);
-  DevBuf counters, hard;
-  CHIP(hipMalloc(&counters.p, 16));
+  DevPtr<unsigned long long> counters;
+  DevPtr<int64_t> hard;
+  DQ_HIP(counters.alloc(2));
   unsigned long long h_counters[2] = {0, 0};
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (f64) CHIP(hipMalloc(&hard.p, (size_t)hard_cap * 8));
-    CHIP(hipMemsetAsync(counters.p, 0, 16, st));
-    auto* dc = static_cast<unsigned long long*>(counters.p);
-    auto* dh = static_cast<int64_t*>(hard.p);
+    if (f64) DQ_HIP(hard.alloc((size_t)hard_cap));
+    DQ_HIP(hipMemsetAsync(counters.get(), 0, 16, st));
+    auto* dc = counters.get();
+    auto* dh = hard.get();
     if (large) {
       if (f64) launch_cast<int64_t, true>(src, n_rows, out_values, out_validity, dc, dh, hard_cap, st);
       else launch_cast<int64_t, false>(src, n_rows, out_values, out_validity, dc, dh, hard_cap, st);
@@ -227,15 +213,14 @@ extern "C" dq_status dq_cast_utf8(int32_t src_type, const dq_column_view* src, i
       if (f64) launch_cast<int32_t, true>(src, n_rows, out_values, out_validity, dc, dh, hard_cap, st);
       else launch_cast<int32_t, false>(src, n_rows, out_values, out_validity, dc, dh, hard_cap, st);
     }
-    CHIP(hipGetLastError());
-    CHIP(hipMemcpyAsync(h_counters, counters.p, 16, hipMemcpyDeviceToHost, st));
-    CHIP(hipStreamSynchronize(st));
+    DQ_HIP(hipGetLastError());
+    DQ_HIP(hipMemcpyAsync(h_counters, counters.get(), 16, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
     if ((int64_t)h_counters[1] <= hard_cap) break;
     if (attempt == 1) return set_error(DQ_E_HIP, "dq_cast_utf8: hard-row count changed between runs");
     // the list overflowed: size it for the reported count and cast again
     hard_cap = (int64_t)h_counters[1];
-    (void)hipFree(hard.p);
-    hard.p = nullptr;
+    hard.reset();
   }
   if (null_count) *null_count = (int64_t)h_counters[0];
   const int64_t nh = (int64_t)h_counters[1];
@@ -243,29 +228,30 @@ extern "C" dq_status dq_cast_utf8(int32_t src_type, const dq_column_view* src, i
 
   // hard tier: gather the rows' bytes, convert on the host, scatter the values
   const unsigned hgrid = (unsigned)((nh + 255) / 256);
-  DevBuf spans, dst, bytes, vals;
-  CHIP(hipMalloc(&spans.p, (size_t)nh * 16));
-  if (large) hipLaunchKernelGGL(dq_cast_hard_spans<int64_t>, dim3(hgrid), dim3(256), 0, st, static_cast<const int64_t*>(src->offsets), static_cast<const int64_t*>(hard.p), nh, static_cast<int64_t*>(spans.p));
-  else hipLaunchKernelGGL(dq_cast_hard_spans<int32_t>, dim3(hgrid), dim3(256), 0, st, static_cast<const int32_t*>(src->offsets), static_cast<const int64_t*>(hard.p), nh, static_cast<int64_t*>(spans.p));
-  CHIP(hipGetLastError());
+  DevPtr<int64_t> spans, dst;
+  DevPtr<uint8_t> bytes;
+  DevPtr<uint64_t> vals;
+  DQ_HIP(spans.alloc((size_t)nh * 2));
+  if (large) hipLaunchKernelGGL(dq_cast_hard_spans<int64_t>, dim3(hgrid), dim3(256), 0, st, static_cast<const int64_t*>(src->offsets), hard.get(), nh, spans.get());
+  else hipLaunchKernelGGL(dq_cast_hard_spans<int32_t>, dim3(hgrid), dim3(256), 0, st, static_cast<const int32_t*>(src->offsets), hard.get(), nh, spans.get());
+  DQ_HIP(hipGetLastError());
   std::vector<int64_t> h_spans((size_t)nh * 2), h_dst((size_t)nh);
-  CHIP(hipMemcpyAsync(h_spans.data(), spans.p, (size_t)nh * 16, hipMemcpyDeviceToHost, st));
-  CHIP(hipStreamSynchronize(st));
+  DQ_HIP(hipMemcpyAsync(h_spans.data(), spans.get(), (size_t)nh * 16, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
   int64_t total = 0;
   for (int64_t i = 0; i < nh; ++i) {
     h_dst[(size_t)i] = total;
     total += h_spans[(size_t)(2 * i + 1)] - h_spans[(size_t)(2 * i)];
   }
-  CHIP(hipMalloc(&dst.p, (size_t)nh * 8));
-  CHIP(hipMalloc(&bytes.p, (size_t)total));
-  CHIP(hipMemcpyAsync(dst.p, h_dst.data(), (size_t)nh * 8, hipMemcpyHostToDevice, st));
+  DQ_HIP(dst.alloc((size_t)nh));
+  DQ_HIP(bytes.alloc((size_t)total));
+  DQ_HIP(hipMemcpyAsync(dst.get(), h_dst.data(), (size_t)nh * 8, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(dq_cast_hard_gather, dim3(hgrid), dim3(256), 0, st, static_cast<const uint8_t*>(src->values),
-                     static_cast<const int64_t*>(spans.p), static_cast<const int64_t*>(dst.p), nh,
-                     static_cast<uint8_t*>(bytes.p));
-  CHIP(hipGetLastError());
+                     spans.get(), dst.get(), nh, bytes.get());
+  DQ_HIP(hipGetLastError());
   std::vector<uint8_t> h_bytes((size_t)total);
-  CHIP(hipMemcpyAsync(h_bytes.data(), bytes.p, (size_t)total, hipMemcpyDeviceToHost, st));
-  CHIP(hipStreamSynchronize(st));
+  DQ_HIP(hipMemcpyAsync(h_bytes.data(), bytes.get(), (size_t)total, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
   std::vector<uint64_t> h_vals((size_t)nh);
   locale_t c_loc = newlocale(LC_ALL_MASK, "C", (locale_t)0);
   if (c_loc == (locale_t)0) return set_error(DQ_E_INVALID, "dq_cast_utf8: newlocale(\"C\") failed");
@@ -275,11 +261,10 @@ extern "C" dq_status dq_cast_utf8(int32_t src_type, const dq_column_view* src, i
                         h_vals[(size_t)i]);
   freelocale(c_loc);
   if (!ok) return set_error(DQ_E_HIP, "dq_cast_utf8: host and device disagree on a hard row");
-  CHIP(hipMalloc(&vals.p, (size_t)nh * 8));
-  CHIP(hipMemcpyAsync(vals.p, h_vals.data(), (size_t)nh * 8, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(dq_cast_hard_scatter, dim3(hgrid), dim3(256), 0, st, static_cast<const int64_t*>(hard.p),
-                     static_cast<const uint64_t*>(vals.p), nh, static_cast<uint64_t*>(out_values));
-  CHIP(hipGetLastError());
-  CHIP(hipStreamSynchronize(st));
+  DQ_HIP(vals.alloc((size_t)nh));
+  DQ_HIP(hipMemcpyAsync(vals.get(), h_vals.data(), (size_t)nh * 8, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(dq_cast_hard_scatter, dim3(hgrid), dim3(256), 0, st, hard.get(), vals.get(), nh, static_cast<uint64_t*>(out_values));
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(hipStreamSynchronize(st));
   return DQ_OK;
 }

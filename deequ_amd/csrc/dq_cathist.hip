@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "dq_hash.h"
-#include "dq_internal.h"
+#include "dq_hip_host.h"
 #include "dq_strkey.h"
 
 namespace dq {
@@ -289,29 +289,6 @@ __global__ __launch_bounds__(kCatBlock) void cat_hist_bool(const CatView* __rest
   }
 }
 
-#define KHIP(x)                                                                                          \
-  do {                                                                                                   \
-    hipError_t e_ = (x);                                                                                 \
-    if (e_ != hipSuccess)                                                                                \
-      return set_error(e_ == hipErrorOutOfMemory ? DQ_E_OOM : DQ_E_HIP, "dq_cat_hist_build: %s: %s", #x, \
-                       hipGetErrorString(e_));                                                           \
-  } while (0)
-
-// a temporary from the device's stream-ordered pool, returned to it in stream order
-struct PoolBuf {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  PoolBuf() = default;
-  PoolBuf(const PoolBuf&) = delete;
-  ~PoolBuf() {
-    if (p) (void)hipFreeAsync(p, s);
-  }
-  hipError_t alloc(size_t bytes, hipStream_t st) {
-    s = st;
-    return hipMallocAsync(&p, std::max<size_t>(bytes, 16), st);
-  }
-};
-
 }  // namespace
 }  // namespace dq
 
@@ -369,7 +346,7 @@ dq_status dq_cat_hist_build(const int32_t* types, int32_t n_cols, const dq_colum
   }
   const uint64_t key_mask = test_hash_mask();
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  KHIP(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
 
   std::vector<CatView> hviews((size_t)n_chunks * n_cols);
   for (size_t i = 0; i < hviews.size(); ++i)
@@ -378,19 +355,19 @@ dq_status dq_cat_hist_build(const int32_t* types, int32_t n_cols, const dq_colum
   hidx.insert(hidx.end(), types, types + n_cols);
   hidx.insert(hidx.end(), str_cols.begin(), str_cols.end());
   hidx.insert(hidx.end(), bool_cols.begin(), bool_cols.end());
-  PoolBuf d_views, d_idx, d_states, d_coll;
-  KHIP(d_views.alloc(hviews.size() * sizeof(CatView), st));
-  KHIP(d_idx.alloc(hidx.size() * sizeof(int32_t), st));
-  KHIP(d_states.alloc((size_t)n_cols * sizeof(CatState), st));
-  KHIP(d_coll.alloc(sizeof(int32_t), st));
-  KHIP(hipMemcpyAsync(d_views.p, hviews.data(), hviews.size() * sizeof(CatView), hipMemcpyHostToDevice, st));
-  KHIP(hipMemcpyAsync(d_idx.p, hidx.data(), hidx.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  KHIP(hipMemsetAsync(d_states.p, 0, (size_t)n_cols * sizeof(CatState), st));
-  KHIP(hipMemsetAsync(d_coll.p, 0, sizeof(int32_t), st));
-  const int32_t* d_types = static_cast<const int32_t*>(d_idx.p);
+  StreamBuf d_views, d_idx, d_states, d_coll;
+  DQ_HIP(d_views.alloc(hviews.size() * sizeof(CatView), st));
+  DQ_HIP(d_idx.alloc(hidx.size() * sizeof(int32_t), st));
+  DQ_HIP(d_states.alloc((size_t)n_cols * sizeof(CatState), st));
+  DQ_HIP(d_coll.alloc(sizeof(int32_t), st));
+  DQ_HIP(hipMemcpyAsync(d_views.get(), hviews.data(), hviews.size() * sizeof(CatView), hipMemcpyHostToDevice, st));
+  DQ_HIP(hipMemcpyAsync(d_idx.get(), hidx.data(), hidx.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  DQ_HIP(hipMemsetAsync(d_states.get(), 0, (size_t)n_cols * sizeof(CatState), st));
+  DQ_HIP(hipMemsetAsync(d_coll.get(), 0, sizeof(int32_t), st));
+  const int32_t* d_types = static_cast<const int32_t*>(d_idx.get());
   const int32_t* d_str = d_types + n_cols;
   const int32_t* d_bool = d_str + str_cols.size();
-  auto* states = static_cast<CatState*>(d_states.p);
+  auto* states = static_cast<CatState*>(d_states.get());
 
   for (int k = 0; k < n_chunks; ++k) {
     const int64_t n = chunk_rows[k];
@@ -404,23 +381,23 @@ dq_status dq_cat_hist_build(const int32_t* types, int32_t n_cols, const dq_colum
       range = std::min(range, kCatMaxRange);
       gx = (n + range - 1) / range;
       hipLaunchKernelGGL(cat_hist_str, dim3((unsigned)gx, (unsigned)str_cols.size()), dim3(kCatBlock), 0, st,
-                         static_cast<const CatView*>(d_views.p), d_types, d_str, n_cols, (int32_t)k, n, range, key_mask,
-                         states, static_cast<int32_t*>(d_coll.p));
-      KHIP(hipGetLastError());
+                         static_cast<const CatView*>(d_views.get()), d_types, d_str, n_cols, (int32_t)k, n, range, key_mask,
+                         states, static_cast<int32_t*>(d_coll.get()));
+      DQ_HIP(hipGetLastError());
     }
     if (!bool_cols.empty()) {
       const int64_t words = (n + 31) / 32;
       const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(1024, (words + kCatBlock * 4 - 1) / (kCatBlock * 4)));
       hipLaunchKernelGGL(cat_hist_bool, dim3((unsigned)gx, (unsigned)bool_cols.size()), dim3(kCatBlock), 0, st,
-                         static_cast<const CatView*>(d_views.p), d_bool, n_cols, (int32_t)k, n, states);
-      KHIP(hipGetLastError());
+                         static_cast<const CatView*>(d_views.get()), d_bool, n_cols, (int32_t)k, n, states);
+      DQ_HIP(hipGetLastError());
     }
   }
   std::vector<CatState> hstates((size_t)n_cols);
   int32_t collided = 0;
-  KHIP(hipMemcpyAsync(hstates.data(), d_states.p, (size_t)n_cols * sizeof(CatState), hipMemcpyDeviceToHost, st));
-  KHIP(hipMemcpyAsync(&collided, d_coll.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  KHIP(hipStreamSynchronize(st));
+  DQ_HIP(hipMemcpyAsync(hstates.data(), d_states.get(), (size_t)n_cols * sizeof(CatState), hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipMemcpyAsync(&collided, d_coll.get(), sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
   if (collided) return set_error(DQ_E_UNSUPPORTED, "dq_freq_build: 64-bit tuple-hash collision between distinct values");
 
   for (int c = 0; c < n_cols; ++c) {

@@ -21,15 +21,15 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <mutex>
+#include <type_traits>
 #include <vector>
 
+#include "dq_arena.h"
 #include "dq_device.h"
 #include "dq_freq_image.h"
 #include "dq_hash.h"
-#include "dq_internal.h"
+#include "dq_hip_host.h"
 #include "dq_prim.h"
 #include "dq_strkey.h"
 
@@ -440,54 +440,48 @@ __global__ void mi_final(const double* __restrict__ part, int32_t nparts, double
   }
 }
 
-#define GHIP(x)                                                                                  \
-  do {                                                                                           \
-    hipError_t e_ = (x);                                                                         \
-    if (e_ != hipSuccess) return set_error(DQ_E_HIP, "%s: %s", #x, hipGetErrorString(e_));      \
-  } while (0)
+using Frame = Arena<DeviceMem>::Frame;
+Arena<DeviceMem> g_arena;  // the scratch of every grouping call (dq_arena.h)
 
-// Scratch buffers come from a per-device arena of named slots that only grows: a GROUP BY over a
-// 62.5 M-row chunk needs ~2 GB of temporaries, and hipMalloc / hipFree of that much per call costs more
-// than the sort itself.  Calls are serialised by g_arena_mu (the arena is shared by all plans).
-std::mutex g_arena_mu;
-struct Slot { void* p = nullptr; size_t cap = 0; };
-std::map<std::pair<int, int>, Slot> g_arena;  // (device, slot) -> buffer
+// out = the frame's next buffer, of `count` elements
+template <typename T> dq_status take(Frame& f, T*& out, size_t count) {
+  size_t want = 0;
+  out = static_cast<T*>(f.take_bytes(count * sizeof(std::conditional_t<std::is_void_v<T>, char, T>), &want));
+  return out ? DQ_OK : set_error(DQ_E_OOM, "hipMalloc(%zu) failed", want);
+}
+template <typename... T> dq_status take_each(Frame& f, size_t count, T*&... out) {  // one buffer of `count` elements each
+  dq_status s = DQ_OK;
+  ((s = s ? s : take(f, out, count)), ...);
+  return s;
+}
 
-struct DevBuf {
-  int dev = 0, slot = 0;
-  void* p = nullptr;
-  DevBuf(int device, int s) : dev(device), slot(s) {}
-  dq_status alloc(size_t bytes) {
-    bytes = std::max<size_t>(bytes, 256);
-    Slot& sl = g_arena[{dev, slot}];
-    if (sl.cap < bytes) {
-      if (sl.p) (void)hipFree(sl.p);
-      sl.p = nullptr;
-      sl.cap = 0;
-      const size_t want = bytes + bytes / 8;  // headroom for the next, slightly larger call
-      if (hipMalloc(&sl.p, want) != hipSuccess) return set_error(DQ_E_OOM, "hipMalloc(%zu) failed", want);
-      sl.cap = want;
-    }
-    p = sl.p;
-    return DQ_OK;
-  }
-  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
+// *out = *src after everything enqueued on s so far (one copy, one synchronisation)
+template <typename T> dq_status read_back(T* out, const void* src, hipStream_t s) {
+  static_assert(std::is_trivially_copyable_v<T>, "read_back copies bytes");
+  DQ_HIP(hipMemcpyAsync(out, src, sizeof(T), hipMemcpyDeviceToHost, s));
+  DQ_HIP(hipStreamSynchronize(s));
+  return DQ_OK;
+}
+// *raised = the flag a kernel may have set: the flag's 8 bytes zeroed, `launch` enqueued, the flag read back
+template <typename Launch> dq_status read_flag(void* d_flag, hipStream_t s, int32_t* raised, Launch&& launch) {
+  DQ_HIP(hipMemsetAsync(d_flag, 0, 8, s));
+  launch();
+  DQ_HIP(hipGetLastError());
+  return read_back(raised, d_flag, s);
+}
+// f(std::true_type / std::false_type): a run-time bool as a template argument
+template <typename F> void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256)); }
 
 // one column of a table's value store (owned: freed with it)
 struct StoreCol {
-  void* values = nullptr;      // the values (fixed width) or the strings' bytes
-  int64_t* offsets = nullptr;  // strings: n + 1 offsets into values
-  int64_t bytes = 0;           // length of values
-  StoreCol() = default;
-  StoreCol(const StoreCol&) = delete;
-  StoreCol& operator=(const StoreCol&) = delete;
-  ~StoreCol() {
-    if (values) (void)hipFree(values);
-    if (offsets) (void)hipFree(offsets);
-  }
+  DevPtr<void> values;      // the values (fixed width) or the strings' bytes
+  DevPtr<int64_t> offsets;  // strings: n + 1 offsets into values
+  int64_t bytes = 0;        // length of values
 };
 
 }  // namespace
@@ -502,22 +496,16 @@ struct dq_freq_table {
   std::vector<int32_t> types;
   int64_t n_groups = 0;
   int64_t n_values = 0;  // rows with all grouping columns non-null
-  uint64_t* d_keys = nullptr;
-  int64_t* d_counts = nullptr;
-  uint64_t* d_rep = nullptr;  // hashed tables built from data: one row id (chunk << 40 | row) per group
-  uint64_t* d_keys2 = nullptr;  // hashed tables: second tuple hash per group (merge collision check)
+  DevPtr<uint64_t> d_keys;
+  DevPtr<int64_t> d_counts;
+  DevPtr<uint64_t> d_rep;    // hashed tables built from data: one row id (chunk << 40 | row) per group
+  DevPtr<uint64_t> d_keys2;  // hashed tables: second tuple hash per group (merge collision check)
   // The value store of a self-contained hashed table (dq_freq_materialize, dq_freq_merge of two such tables,
   // dq_freq_from_bytes): per grouping column the n_groups representative values in group order, laid out as one more
   // input chunk without validity -- a dense array of dq_freq_elem_size(type) bytes per value (a BOOL one byte), or
   // int64 offsets[n_groups + 1] and the bytes for strings -- so that store_cols() reads group g's tuple as row g.
   bool has_store = false;
   StoreCol store[kMaxGroupCols];
-  ~dq_freq_table() {
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_keys2) (void)hipFree(d_keys2);
-    if (d_counts) (void)hipFree(d_counts);
-    if (d_rep) (void)hipFree(d_rep);
-  }
 };
 
 namespace dq {
@@ -827,43 +815,44 @@ __global__ void find_groups(const uint64_t* __restrict__ want, int32_t n, const 
 }  // namespace
 }  // namespace dq
 
-static dq_status rle_into(dq_freq_table* t, const uint64_t* sorted, int64_t n, const uint64_t* sorted_rows = nullptr) {
-  DevBuf nruns(t->device, 20), tmp(t->device, 21), starts(t->device, 22);
-  if (dq_status s = nruns.alloc(sizeof(int64_t))) return s;
-  GHIP(hipMalloc(&t->d_keys, std::max<int64_t>(1, n) * sizeof(uint64_t)));
-  GHIP(hipMalloc(&t->d_counts, std::max<int64_t>(1, n) * sizeof(int64_t)));
+static dq_status rle_into(Frame& fr, dq_freq_table* t, const uint64_t* sorted, int64_t n,
+                          const uint64_t* sorted_rows = nullptr) {
+  int64_t *nruns = nullptr, *starts = nullptr;
+  void* tmp = nullptr;
+  if (dq_status s = take(fr, nruns, 1)) return s;
+  DQ_HIP(t->d_keys.alloc(std::max<int64_t>(1, n)));
+  DQ_HIP(t->d_counts.alloc(std::max<int64_t>(1, n)));
   if (n == 0) { t->n_groups = 0; return DQ_OK; }
-  if (dq_status s = tmp.alloc(prim::runs_temp_bytes(n))) return s;
-  if (dq_status s = starts.alloc((size_t)n * 8)) return s;
-  GHIP(prim::runs(sorted, n, t->d_keys, starts.as<int64_t>(), t->d_counts, nruns.as<int64_t>(), tmp.p, t->stream));
-  GHIP(hipMemcpyAsync(&t->n_groups, nruns.p, sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipStreamSynchronize(t->stream));
+  if (dq_status s = take(fr, tmp, prim::runs_temp_bytes(n))) return s;
+  if (dq_status s = take(fr, starts, n)) return s;
+  DQ_HIP(prim::runs(sorted, n, t->d_keys.get(), starts, t->d_counts.get(), nruns, tmp, t->stream));
+  if (dq_status s = read_back(&t->n_groups, nruns, t->stream)) return s;
   if (sorted_rows && t->n_groups > 0) {  // representative row of every group (Histogram renders its value)
-    GHIP(hipMalloc(&t->d_rep, t->n_groups * 8));
-    hipLaunchKernelGGL(gather_rep, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, sorted_rows,
-                       starts.as<int64_t>(), t->n_groups, t->d_rep);
-    GHIP(hipGetLastError());
-    GHIP(hipStreamSynchronize(t->stream));
+    DQ_HIP(t->d_rep.alloc(t->n_groups));
+    hipLaunchKernelGGL(gather_rep, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, sorted_rows, starts,
+                       t->n_groups, t->d_rep.get());
+    DQ_HIP(hipGetLastError());
+    DQ_HIP(hipStreamSynchronize(t->stream));
   }
   return DQ_OK;
 }
 
-// the exact check of equal-hash neighbours in sorted order (verify_runs); nsel's first word is the collision flag
+static dq_status collision_status(int32_t coll) {
+  return coll ? set_error(DQ_E_UNSUPPORTED, "dq_freq_build: 64-bit tuple-hash collision between distinct values") : DQ_OK;
+}
+
+// the exact check of equal-hash neighbours in sorted order (verify_runs); d_flag: 8 bytes for the collision flag
 static dq_status verify_sorted(dq_freq_table* t, const uint64_t* sorted_keys, const uint64_t* sorted_rows, int64_t nv,
-                               const std::vector<GroupCols>& gcs, DevBuf& d_chunks, DevBuf& nsel) {
-  GHIP(hipMemsetAsync(nsel.p, 0, 8, t->stream));
-  if (gcs.size() == 1)
-    hipLaunchKernelGGL(verify_runs<true>, dim3(grid_for(nv)), dim3(256), 0, t->stream, sorted_keys, sorted_rows, nv,
-                       d_chunks.as<GroupCols>(), gcs[0], nsel.as<int32_t>());
-  else
-    hipLaunchKernelGGL(verify_runs<false>, dim3(grid_for(nv)), dim3(256), 0, t->stream, sorted_keys, sorted_rows, nv,
-                       d_chunks.as<GroupCols>(), gcs[0], nsel.as<int32_t>());
-  GHIP(hipGetLastError());
+                               const std::vector<GroupCols>& gcs, const GroupCols* d_chunks, int32_t* d_flag) {
   int32_t coll = 0;
-  GHIP(hipMemcpyAsync(&coll, nsel.p, 4, hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipStreamSynchronize(t->stream));
-  if (coll) return set_error(DQ_E_UNSUPPORTED, "dq_freq_build: 64-bit tuple-hash collision between distinct values");
-  return DQ_OK;
+  if (dq_status s = read_flag(d_flag, t->stream, &coll, [&] {
+        with_bool(gcs.size() == 1, [&](auto one) {
+          hipLaunchKernelGGL(verify_runs<decltype(one)::value>, dim3(grid_for(nv)), dim3(256), 0, t->stream, sorted_keys,
+                             sorted_rows, nv, d_chunks, gcs[0], d_flag);
+        });
+      }))
+    return s;
+  return collision_status(coll);
 }
 
 // The dictionary form of a table (no sort): when an evenly spaced sample of the compacted keys holds at most
@@ -871,8 +860,8 @@ static dq_status verify_sorted(dq_freq_table* t, const uint64_t* sorted_keys, co
 // pass; the groups are then those keys in ascending order -- what the sort and its runs yield -- with the smallest
 // sampled row id of each as its representative.  A key outside the sample (a group the sample missed) sets
 // *done = false and the caller sorts.  DQ_GROUP_DICT=0 turns it off, =1 lifts the size thresholds (tests).
-static dq_status dict_table(dq_freq_table* t, const uint64_t* keys, const uint64_t* rows, int64_t nv, int end_bit,
-                            bool* done) {
+static dq_status dict_table(Frame& fr, dq_freq_table* t, const uint64_t* keys, const uint64_t* rows, int64_t nv,
+                            int end_bit, bool* done) {
   *done = false;
   const char* knob = std::getenv("DQ_GROUP_DICT");
   const bool forced = knob && knob[0] == '1';
@@ -880,61 +869,55 @@ static dq_status dict_table(dq_freq_table* t, const uint64_t* keys, const uint64
   // only where the sort would run 5+ digit passes (tuple hashes, wide numeric keys) over 1 M+ keys: a table the
   // form declines pays ~0.15 ms (the sample's sort and read-back), measured against 4.0 ms for 1e8 27-bit keys
   if (!forced && (nv < (int64_t)1 << 20 || end_bit <= 32)) return DQ_OK;
-  const int D = t->device;
+  const hipStream_t S = t->stream;
   const int m = (int)std::min<int64_t>(kDictSample, nv);
-  DevBuf sk(D, 50), sr(D, 51), sks(D, 52), nr(D, 54), tmp(D, 55);
-  if (dq_status s = sk.alloc((size_t)m * 8)) return s;
-  if (dq_status s = sks.alloc((size_t)m * 8)) return s;
-  if (dq_status s = nr.alloc(16)) return s;
+  uint64_t *sk = nullptr, *sks = nullptr, *sr = nullptr, *dict = nullptr;
+  int64_t* nr = nullptr;  // the number of distinct sample keys, then (second word) the miss flag
+  void* tmp = nullptr;
+  if (dq_status s = take_each(fr, m, sk, sks)) return s;
+  if (dq_status s = take(fr, nr, 2)) return s;
   if (rows)
-    if (dq_status s = sr.alloc((size_t)m * 8)) return s;
+    if (dq_status s = take(fr, sr, m)) return s;
   const size_t tb = prim::sort_temp_bytes(m, 0);
-  if (dq_status s = tmp.alloc(tb)) return s;
-  hipLaunchKernelGGL(dict_sample, dim3((m + 255) / 256), dim3(256), 0, t->stream, keys, rows, nv, m, sk.as<uint64_t>(),
-                     rows ? sr.as<uint64_t>() : nullptr);
-  GHIP(hipGetLastError());
+  if (dq_status s = take(fr, tmp, tb)) return s;
+  hipLaunchKernelGGL(dict_sample, dim3((m + 255) / 256), dim3(256), 0, S, keys, rows, nv, m, sk, sr);
+  DQ_HIP(hipGetLastError());
   // keys only: a table the form does not take costs this sort of 16 K keys, one small kernel and one read-back
-  GHIP(prim::sort_pairs(sk.as<uint64_t>(), sks.as<uint64_t>(), nullptr, nullptr, 0, m, 0, end_bit, false, tmp.p, tb,
-                        t->stream));
-  DevBuf dict(D, 53);
-  if (dq_status s = dict.alloc((size_t)m * 8)) return s;
-  hipLaunchKernelGGL(dict_unique, dim3(1), dim3(1024), 0, t->stream, sks.as<uint64_t>(), m, dict.as<uint64_t>(),
-                     nr.as<int64_t>());
-  GHIP(hipGetLastError());
+  DQ_HIP(prim::sort_pairs(sk, sks, nullptr, nullptr, 0, m, 0, end_bit, false, tmp, tb, S));
+  if (dq_status s = take(fr, dict, m)) return s;
+  hipLaunchKernelGGL(dict_unique, dim3(1), dim3(1024), 0, S, sks, m, dict, nr);
+  DQ_HIP(hipGetLastError());
   int64_t nd = 0;
-  GHIP(hipMemcpyAsync(&nd, nr.p, 8, hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipStreamSynchronize(t->stream));
+  if (dq_status s = read_back(&nd, nr, S)) return s;
   if (nd < 1 || nd > kDictMax || (!forced && nd * 16 > m)) return DQ_OK;
   int pw = 1;
   while (pw < nd) pw <<= 1;
-  GHIP(hipMalloc(&t->d_keys, (size_t)nd * 8));
-  GHIP(hipMalloc(&t->d_counts, (size_t)nd * 8));
-  GHIP(hipMemcpyAsync(t->d_keys, dict.p, (size_t)nd * 8, hipMemcpyDeviceToDevice, t->stream));
-  GHIP(hipMemsetAsync(t->d_counts, 0, (size_t)nd * 8, t->stream));
-  GHIP(hipMemsetAsync(nr.as<char>() + 8, 0, 4, t->stream));
+  // the table's arrays stay local until every key is known to be in the dictionary
+  DevPtr<uint64_t> d_keys, d_rep;
+  DevPtr<int64_t> d_counts;
+  int32_t* const d_miss = reinterpret_cast<int32_t*>(nr + 1);
+  DQ_HIP(d_keys.alloc(nd));
+  DQ_HIP(d_counts.alloc(nd));
+  DQ_HIP(hipMemcpyAsync(d_keys.get(), dict, (size_t)nd * 8, hipMemcpyDeviceToDevice, S));
+  DQ_HIP(hipMemsetAsync(d_counts.get(), 0, (size_t)nd * 8, S));
+  DQ_HIP(hipMemsetAsync(d_miss, 0, 4, S));
   if (rows) {
-    GHIP(hipMalloc(&t->d_rep, (size_t)nd * 8));
-    GHIP(hipMemsetAsync(t->d_rep, 0xFF, (size_t)nd * 8, t->stream));
-    hipLaunchKernelGGL(dict_rep, dim3((m + 255) / 256), dim3(256), 0, t->stream, sk.as<uint64_t>(), sr.as<uint64_t>(), m,
-                       t->d_keys, (int)nd, reinterpret_cast<unsigned long long*>(t->d_rep));
-    GHIP(hipGetLastError());
+    DQ_HIP(d_rep.alloc(nd));
+    DQ_HIP(hipMemsetAsync(d_rep.get(), 0xFF, (size_t)nd * 8, S));
+    hipLaunchKernelGGL(dict_rep, dim3((m + 255) / 256), dim3(256), 0, S, sk, sr, m, d_keys.get(), (int)nd,
+                       d_rep.as<unsigned long long>());
+    DQ_HIP(hipGetLastError());
   }
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (nv + 256 * kDictPer - 1) / (256 * kDictPer)));
-  hipLaunchKernelGGL(dict_count, dim3(grid), dim3(256), 0, t->stream, keys, nv, t->d_keys, (int)nd, pw,
-                     reinterpret_cast<unsigned long long*>(t->d_counts), reinterpret_cast<int32_t*>(nr.as<char>() + 8));
-  GHIP(hipGetLastError());
+  hipLaunchKernelGGL(dict_count, dim3(grid), dim3(256), 0, S, keys, nv, d_keys.get(), (int)nd, pw,
+                     d_counts.as<unsigned long long>(), d_miss);
+  DQ_HIP(hipGetLastError());
   int32_t miss = 0;
-  GHIP(hipMemcpyAsync(&miss, nr.as<char>() + 8, 4, hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipStreamSynchronize(t->stream));
-  if (miss) {  // a group outside the sample: back to the sort (the caller allocates the table's arrays afresh)
-    (void)hipFree(t->d_keys);
-    (void)hipFree(t->d_counts);
-    if (t->d_rep) (void)hipFree(t->d_rep);
-    t->d_keys = nullptr;
-    t->d_counts = nullptr;
-    t->d_rep = nullptr;
-    return DQ_OK;
-  }
+  if (dq_status s = read_back(&miss, d_miss, S)) return s;
+  if (miss) return DQ_OK;  // a group outside the sample: back to the sort
+  t->d_keys = std::move(d_keys);
+  t->d_counts = std::move(d_counts);
+  t->d_rep = std::move(d_rep);
   t->n_groups = nd;
   *done = true;
   return DQ_OK;
@@ -948,8 +931,8 @@ static GroupCols store_cols(const dq_freq_table* t) {
   g.key_mask = test_hash_mask();
   for (int c = 0; c < g.n_cols; ++c) {
     const int32_t ty = t->types[c];
-    g.values[c] = t->store[c].values;
-    g.offsets[c] = t->store[c].offsets;
+    g.values[c] = t->store[c].values.get();
+    g.offsets[c] = t->store[c].offsets.get();
     g.type[c] = ty == DQ_TYPE_UTF8 ? DQ_TYPE_LARGE_UTF8 : ty == DQ_TYPE_BOOL ? DQ_TYPE_I8 : ty;
   }
   return g;
@@ -961,34 +944,49 @@ static int64_t wave_copy_len() {  // DQ_FREQ_WAVE_COPY: the lane / wave switch l
   return v > 0 ? v : kWaveCopyLen;
 }
 
+// the chunk descriptor of one chunk's row of views (n_cols of them); a gather of non-null rows carries no validity
+static GroupCols view_cols(const int32_t* types, int n_cols, const dq_column_view* row, uint64_t key_mask,
+                           bool with_validity) {
+  GroupCols g;
+  std::memset(&g, 0, sizeof(g));
+  g.n_cols = n_cols;
+  g.key_mask = key_mask;
+  for (int c = 0; c < n_cols; ++c) {
+    g.values[c] = row[c].values;
+    if (with_validity) g.validity[c] = reinterpret_cast<const uint32_t*>(row[c].validity);
+    g.offsets[c] = row[c].offsets;
+    g.type[c] = types[c];
+  }
+  return g;
+}
+
 // Column c (type code `type`) of the tuples at row ids d_rep[0 .. G) of the chunks d_chunks, gathered into *out
-// (allocated here, owned by the caller's StoreCol).  The caller holds g_arena_mu and has checked the row ids.
-static dq_status gather_column(int D, hipStream_t S, const GroupCols* d_chunks, const uint64_t* d_rep, int64_t G, int c,
-                               int32_t type, StoreCol* out) {
+// (allocated here, owned by the caller's StoreCol).  The caller has checked the row ids; scan_tmp is its frame's
+// buffer of prim::scan_temp_bytes(G + 1) bytes (one for all the columns it gathers).
+static dq_status gather_column(hipStream_t S, const GroupCols* d_chunks, const uint64_t* d_rep, int64_t G, int c,
+                               int32_t type, void* scan_tmp, StoreCol* out) {
   const int es = dq_freq_elem_size(type);
   if (es < 0) return set_error(DQ_E_TYPE, "frequency table: unknown type code %d", type);
   if (es > 0) {
     out->bytes = G * es;
-    GHIP(hipMalloc(&out->values, std::max<int64_t>(8, out->bytes)));
+    DQ_HIP(out->values.alloc(std::max<int64_t>(8, out->bytes)));
     if (G > 0) {
-      hipLaunchKernelGGL(gather_fixed, dim3(grid_for(G)), dim3(256), 0, S, d_rep, G, d_chunks, c, es, out->values);
-      GHIP(hipGetLastError());
+      hipLaunchKernelGGL(gather_fixed, dim3(grid_for(G)), dim3(256), 0, S, d_rep, G, d_chunks, c, es, out->values.get());
+      DQ_HIP(hipGetLastError());
     }
     return DQ_OK;
   }
-  DevBuf tmp(D, 62);
-  if (dq_status s = tmp.alloc(prim::scan_temp_bytes(G + 1))) return s;
-  GHIP(hipMalloc(&out->offsets, (G + 1) * 8));
-  hipLaunchKernelGGL(gather_str_lens, dim3(grid_for(G + 1)), dim3(256), 0, S, d_rep, G, d_chunks, c, out->offsets);
-  GHIP(hipGetLastError());
-  GHIP(prim::exclusive_sum_i64(out->offsets, out->offsets, G + 1, tmp.p, S));
-  GHIP(hipMemcpyAsync(&out->bytes, out->offsets + G, 8, hipMemcpyDeviceToHost, S));
-  GHIP(hipStreamSynchronize(S));
-  GHIP(hipMalloc(&out->values, std::max<int64_t>(8, out->bytes)));
+  DQ_HIP(out->offsets.alloc(G + 1));
+  int64_t* const offs = out->offsets.get();
+  hipLaunchKernelGGL(gather_str_lens, dim3(grid_for(G + 1)), dim3(256), 0, S, d_rep, G, d_chunks, c, offs);
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(prim::exclusive_sum_i64(offs, offs, G + 1, scan_tmp, S));
+  if (dq_status s = read_back(&out->bytes, offs + G, S)) return s;
+  DQ_HIP(out->values.alloc(std::max<int64_t>(8, out->bytes)));
   if (G > 0 && out->bytes > 0) {
-    hipLaunchKernelGGL(gather_str_bytes, dim3(grid_for(G)), dim3(256), 0, S, d_rep, G, d_chunks, c, out->offsets,
-                       reinterpret_cast<uint8_t*>(out->values), wave_copy_len());
-    GHIP(hipGetLastError());
+    hipLaunchKernelGGL(gather_str_bytes, dim3(grid_for(G)), dim3(256), 0, S, d_rep, G, d_chunks, c, offs,
+                       out->values.as<uint8_t>(), wave_copy_len());
+    DQ_HIP(hipGetLastError());
   }
   return DQ_OK;
 }
@@ -996,8 +994,8 @@ static dq_status gather_column(int D, hipStream_t S, const GroupCols* d_chunks, 
 extern "C" {
 
 struct MiRequest { double total; double* value; int32_t* defined; };
-static dq_status mi_from_joint(dq_freq_table* t, const uint64_t* sorted_keys, const uint64_t* sorted_rows, int64_t nv,
-                               const GroupCols* d_chunks, const MiRequest& mi);
+static dq_status mi_from_joint(Frame& fr, dq_freq_table* t, const uint64_t* sorted_keys, const uint64_t* sorted_rows,
+                               int64_t nv, const GroupCols* d_chunks, const MiRequest& mi);
 
 static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_column_view* cols,
                                  const int64_t* chunk_rows, int32_t n_chunks, int32_t device, void* hip_stream,
@@ -1018,7 +1016,7 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
     total += chunk_rows[k];
   }
   if (total >= (1ll << 31)) return set_error(DQ_E_UNSUPPORTED, "dq_freq_build: at most 2^31 - 1 rows per table");
-  GHIP(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   auto* t = new dq_freq_table();
   std::unique_ptr<dq_freq_table> guard(t);
   t->device = device;
@@ -1031,192 +1029,164 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
   // test hook: keep only some bits of the primary tuple hash, to force collisions between distinct tuples
   const uint64_t key_mask = test_hash_mask();
   std::vector<GroupCols> gcs(std::max(1, n_chunks));
-  for (int k = 0; k < n_chunks; ++k) {
-    GroupCols& g = gcs[k];
-    std::memset(&g, 0, sizeof(g));
-    g.n_cols = n_cols;
-    g.key_mask = key_mask;
-    for (int c = 0; c < n_cols; ++c) {
-      const dq_column_view& v = cols[(size_t)k * n_cols + c];
-      g.values[c] = v.values;
-      g.validity[c] = reinterpret_cast<const uint32_t*>(v.validity);
-      g.offsets[c] = v.offsets;
-      g.type[c] = types[c];
-    }
-  }
-  std::lock_guard<std::mutex> lock(g_arena_mu);
-  const int D = device;
-  DevBuf sel_keys(D, 2), sel_rows(D, 4), nsel(D, 5), tmp(D, 6), sorted_keys(D, 7), sorted_rows(D, 8), d_chunks(D, 9);
-  if (dq_status s = nsel.alloc(24)) return s;
-  if (dq_status s = sel_keys.alloc(std::max<int64_t>(1, total) * 8)) return s;
-  if (t->hashed) {
-    if (dq_status s = sel_rows.alloc(std::max<int64_t>(1, total) * 8)) return s;
-  }
-  int64_t nv = 0;
-  const unsigned long long cur0[3] = {0ull, ~0ull, 0ull};  // count, AND, OR of the appended keys
-  GHIP(hipMemcpyAsync(nsel.p, cur0, sizeof(cur0), hipMemcpyHostToDevice, t->stream));
+  for (int k = 0; k < n_chunks; ++k) gcs[k] = view_cols(types, n_cols, cols + (size_t)k * n_cols, key_mask, true);
+  Frame fr(g_arena, device);
+  const hipStream_t S = t->stream;
+  uint64_t *sel_keys = nullptr, *sel_rows = nullptr, *sorted_keys = nullptr, *sorted_rows = nullptr;
+  unsigned long long* nsel = nullptr;  // count, AND, OR of the appended keys; later the checks' collision flag
+  GroupCols* d_chunks = nullptr;
+  void* tmp = nullptr;
+  if (dq_status s = take(fr, nsel, 3)) return s;
+  int32_t* const d_flag = reinterpret_cast<int32_t*>(nsel);
+  if (dq_status s = take(fr, sel_keys, std::max<int64_t>(1, total))) return s;
+  if (t->hashed)
+    if (dq_status s = take(fr, sel_rows, std::max<int64_t>(1, total))) return s;
+  const unsigned long long cur0[3] = {0ull, ~0ull, 0ull};
+  DQ_HIP(hipMemcpyAsync(nsel, cur0, sizeof(cur0), hipMemcpyHostToDevice, S));
   for (int k = 0; k < n_chunks; ++k) {
     const int64_t n = chunk_rows[k];
     if (n == 0) continue;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + kCompactRows - 1) / kCompactRows));
-    if (t->hashed)
-      hipLaunchKernelGGL(group_compact<true>, dim3(grid), dim3(256), 0, t->stream, gcs[k], n, (int64_t)k,
-                         sel_keys.as<uint64_t>(), sel_rows.as<uint64_t>(), nsel.as<unsigned long long>());
-    else
-      hipLaunchKernelGGL(group_compact<false>, dim3(grid), dim3(256), 0, t->stream, gcs[k], n, (int64_t)k,
-                         sel_keys.as<uint64_t>(), nullptr, nsel.as<unsigned long long>());
-    GHIP(hipGetLastError());
+    with_bool(t->hashed != 0, [&](auto hashed) {  // (sel_rows is NULL for an exact-key table)
+      hipLaunchKernelGGL(group_compact<decltype(hashed)::value>, dim3(grid), dim3(256), 0, S, gcs[k], n, (int64_t)k,
+                         sel_keys, sel_rows, nsel);
+    });
+    DQ_HIP(hipGetLastError());
   }
   unsigned long long cur[3];
-  GHIP(hipMemcpyAsync(cur, nsel.p, sizeof(cur), hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipStreamSynchronize(t->stream));
-  nv = (int64_t)cur[0];
+  if (dq_status s = read_back(&cur, nsel, S)) return s;
+  const int64_t nv = (int64_t)cur[0];
   // the keys agree above their highest differing bit: sorting bits [0, end_bit) gives the same order as all 64
   // (small-range integer columns: 2 digit passes instead of 6)
   const uint64_t differ = nv > 0 ? (uint64_t)(cur[1] ^ cur[2]) : 0ull;
   const int end_bit = differ ? 64 - __builtin_clzll(differ) : 1;
   t->n_values = nv;
   if (t->hashed) {
-    if (dq_status s = d_chunks.alloc(gcs.size() * sizeof(GroupCols))) return s;
-    GHIP(hipMemcpyAsync(d_chunks.p, gcs.data(), gcs.size() * sizeof(GroupCols), hipMemcpyHostToDevice, t->stream));
+    if (dq_status s = take(fr, d_chunks, gcs.size())) return s;
+    DQ_HIP(hipMemcpyAsync(d_chunks, gcs.data(), gcs.size() * sizeof(GroupCols), hipMemcpyHostToDevice, S));
   }
   static const char* force = std::getenv("DQ_GROUP_VERIFY");  // A/B knob: "sorted" / "compacted"
   bool dict = false;  // low cardinality: the dictionary form (no sort; the check in compaction order)
   if (!mi && nv > 0 && !(force && force[0] == 's'))
-    if (dq_status s = dict_table(t, sel_keys.as<uint64_t>(), t->hashed ? sel_rows.as<uint64_t>() : nullptr, nv,
-                                 end_bit, &dict))
-      return s;
-  if (dq_status s = sorted_keys.alloc(std::max<int64_t>(1, nv) * 8)) return s;
+    if (dq_status s = dict_table(fr, t, sel_keys, sel_rows, nv, end_bit, &dict)) return s;
+  if (dq_status s = take(fr, sorted_keys, std::max<int64_t>(1, nv))) return s;
   if (nv > 0 && !dict) {
     if (t->hashed) {
-      if (dq_status s = sorted_rows.alloc(nv * 8)) return s;
+      if (dq_status s = take(fr, sorted_rows, nv)) return s;
       const size_t tb = prim::sort_temp_bytes(nv, 8);
-      if (dq_status s = tmp.alloc(tb)) return s;
-      GHIP(prim::sort_pairs(sel_keys.as<uint64_t>(), sorted_keys.as<uint64_t>(), sel_rows.as<uint64_t>(),
-                            sorted_rows.as<uint64_t>(), 8, nv, 0, end_bit, false, tmp.p, tb, t->stream));
+      if (dq_status s = take(fr, tmp, tb)) return s;
+      DQ_HIP(prim::sort_pairs(sel_keys, sorted_keys, sel_rows, sorted_rows, 8, nv, 0, end_bit, false, tmp, tb, S));
       // exact check of equal-hash neighbours in sorted order here for MutualInformation; the frequency table's runs
       // choose between the two forms below
       if (mi)
-        if (dq_status s = verify_sorted(t, sorted_keys.as<uint64_t>(), sorted_rows.as<uint64_t>(), nv, gcs, d_chunks, nsel))
-          return s;
+        if (dq_status s = verify_sorted(t, sorted_keys, sorted_rows, nv, gcs, d_chunks, d_flag)) return s;
     } else {
       const size_t tb = prim::sort_temp_bytes(nv, 0);
-      if (dq_status s = tmp.alloc(tb)) return s;
-      GHIP(prim::sort_pairs(sel_keys.as<uint64_t>(), sorted_keys.as<uint64_t>(), nullptr, nullptr, 0, nv, 0, end_bit,
-                            false, tmp.p, tb, t->stream));
+      if (dq_status s = take(fr, tmp, tb)) return s;
+      DQ_HIP(prim::sort_pairs(sel_keys, sorted_keys, nullptr, nullptr, 0, nv, 0, end_bit, false, tmp, tb, S));
     }
   }
-  if (mi) return mi_from_joint(t, sorted_keys.as<uint64_t>(), sorted_rows.as<uint64_t>(), nv, d_chunks.as<GroupCols>(), *mi);
+  if (mi) return mi_from_joint(fr, t, sorted_keys, sorted_rows, nv, d_chunks, *mi);
   if (!dict)
-    if (dq_status s = rle_into(t, sorted_keys.as<uint64_t>(), nv, t->hashed ? sorted_rows.as<uint64_t>() : nullptr))
-      return s;
+    if (dq_status s = rle_into(fr, t, sorted_keys, nv, t->hashed ? sorted_rows : nullptr)) return s;
   if (t->hashed && nv > 0) {
     // few groups (rows repeat their group's tuple many times): each row checked against its group's representative
     // in compaction order; otherwise equal-hash neighbours in sorted order (which the dictionary form has not made)
     const bool compacted = dict || (force ? force[0] == 'c'
                                           : t->n_groups <= kCompactedMaxGroups && t->n_groups * kRowOrderVerify <= nv);
     if (compacted) {
-      GHIP(hipMemsetAsync(nsel.p, 0, 8, t->stream));
-      if (gcs.size() == 1)
-        hipLaunchKernelGGL(verify_compacted<true>, dim3(grid_for(nv)), dim3(256), 0, t->stream, sel_keys.as<uint64_t>(),
-                           sel_rows.as<uint64_t>(), nv, t->d_keys, t->n_groups, t->d_rep, d_chunks.as<GroupCols>(),
-                           gcs[0], nsel.as<int32_t>());
-      else
-        hipLaunchKernelGGL(verify_compacted<false>, dim3(grid_for(nv)), dim3(256), 0, t->stream,
-                           sel_keys.as<uint64_t>(), sel_rows.as<uint64_t>(), nv, t->d_keys, t->n_groups, t->d_rep,
-                           d_chunks.as<GroupCols>(), gcs[0], nsel.as<int32_t>());
-      GHIP(hipGetLastError());
       int32_t coll = 0;
-      GHIP(hipMemcpyAsync(&coll, nsel.p, 4, hipMemcpyDeviceToHost, t->stream));
-      GHIP(hipStreamSynchronize(t->stream));
-      if (coll) return set_error(DQ_E_UNSUPPORTED, "dq_freq_build: 64-bit tuple-hash collision between distinct values");
-    } else if (dq_status s = verify_sorted(t, sorted_keys.as<uint64_t>(), sorted_rows.as<uint64_t>(), nv, gcs, d_chunks,
-                                          nsel)) {
+      if (dq_status s = read_flag(d_flag, S, &coll, [&] {
+            with_bool(gcs.size() == 1, [&](auto one) {
+              hipLaunchKernelGGL(verify_compacted<decltype(one)::value>, dim3(grid_for(nv)), dim3(256), 0, S, sel_keys,
+                                 sel_rows, nv, t->d_keys.get(), t->n_groups, t->d_rep.get(), d_chunks, gcs[0], d_flag);
+            });
+          }))
+        return s;
+      if (dq_status s = collision_status(coll)) return s;
+    } else if (dq_status s = verify_sorted(t, sorted_keys, sorted_rows, nv, gcs, d_chunks, d_flag)) {
       return s;
     }
   }
   if (t->hashed) {
-    GHIP(hipMalloc(&t->d_keys2, std::max<int64_t>(1, t->n_groups) * 8));
+    DQ_HIP(t->d_keys2.alloc(std::max<int64_t>(1, t->n_groups)));
     if (t->n_groups > 0) {
-      hipLaunchKernelGGL(group_keys2, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, t->d_rep, t->n_groups,
-                         d_chunks.as<GroupCols>(), t->d_keys2);
-      GHIP(hipGetLastError());
-      GHIP(hipStreamSynchronize(t->stream));
+      hipLaunchKernelGGL(group_keys2, dim3(grid_for(t->n_groups)), dim3(256), 0, S, t->d_rep.get(), t->n_groups, d_chunks,
+                         t->d_keys2.get());
+      DQ_HIP(hipGetLastError());
+      DQ_HIP(hipStreamSynchronize(S));
     }
   }
   *out = guard.release();
   return DQ_OK;
 }
 
+// the temporary of the MutualInformation stages over n keys (runs, sorts and scans share it)
+static size_t mi_temp_bytes(int64_t n) {
+  return std::max({prim::runs_temp_bytes(n), prim::sort_temp_bytes(n, 8), prim::scan_temp_bytes(n)});
+}
+
 // the marginals and the sum over G joint groups (counts gc; group g's representative row id rep[g], per-column keys
-// xk / yk, idx[g] = g): shared by the one-pass path (rows of the input) and the state path (rows of the store)
-static dq_status mi_from_groups(int D, hipStream_t S, int64_t G, const int64_t* gc, const uint64_t* rep, const uint64_t* xk,
-                                const uint64_t* yk, const uint64_t* idx, const GroupCols* d_chunks, const MiRequest& mi) {
-  DevBuf sk(D, 38), sidx(D, 39), head(D, 40), seg(D, 41), segsum(D, 42), px(D, 43), py(D, 44), tmp(D, 45), part(D, 46),
-      res(D, 47), coll(D, 48);
-  for (DevBuf* b : {&sk, &sidx, &segsum, &px, &py})
-    if (dq_status s = b->alloc(G * 8)) return s;
-  for (DevBuf* b : {&head, &seg})
-    if (dq_status s = b->alloc(G * 4)) return s;
-  for (DevBuf* b : {&res, &coll})
-    if (dq_status s = b->alloc(8)) return s;
-  if (dq_status s = part.alloc(kSumBlocks * sizeof(double))) return s;
-  const size_t tb = std::max({prim::runs_temp_bytes(G), prim::sort_temp_bytes(G, 8), prim::scan_temp_bytes(G)});
-  if (dq_status s = tmp.alloc(tb)) return s;
-  GHIP(hipMemsetAsync(coll.p, 0, 8, S));
+// xk / yk, idx[g] = g): shared by the one-pass path (rows of the input) and the state path (rows of the store);
+// tmp: the caller's buffer of at least mi_temp_bytes(G) bytes
+static dq_status mi_from_groups(Frame& fr, hipStream_t S, int64_t G, const int64_t* gc, const uint64_t* rep,
+                                const uint64_t* xk, const uint64_t* yk, const uint64_t* idx, const GroupCols* d_chunks,
+                                void* tmp, const MiRequest& mi) {
+  uint64_t *sk = nullptr, *sidx = nullptr;
+  unsigned long long* segsum = nullptr;
+  int64_t *px = nullptr, *py = nullptr;
+  uint32_t *head = nullptr, *seg = nullptr;
+  double *res = nullptr, *part = nullptr;
+  int32_t* coll = nullptr;
+  if (dq_status s = take_each(fr, G, sk, sidx, segsum, px, py, head, seg)) return s;
+  if (dq_status s = take(fr, res, 1)) return s;
+  if (dq_status s = take(fr, coll, 2)) return s;
+  if (dq_status s = take(fr, part, kSumBlocks)) return s;
+  const size_t tb = mi_temp_bytes(G);
+  DQ_HIP(hipMemsetAsync(coll, 0, 8, S));
   for (int c = 0; c < 2; ++c) {
-    GHIP(prim::sort_pairs(c == 0 ? xk : yk, sk.as<uint64_t>(), idx, sidx.as<uint64_t>(), 8, G, 0, 64, false, tmp.p, tb, S));
-    hipLaunchKernelGGL(mi_heads, dim3(grid_for(G)), dim3(256), 0, S, sk.as<uint64_t>(), sidx.as<uint64_t>(), rep, G,
-                       d_chunks, c, head.as<uint32_t>(), coll.as<int32_t>());
-    GHIP(hipGetLastError());
-    GHIP(prim::inclusive_sum_u32(head.as<uint32_t>(), seg.as<uint32_t>(), G, tmp.p, S));
-    GHIP(hipMemsetAsync(segsum.p, 0, G * 8, S));
-    hipLaunchKernelGGL(mi_segsum, dim3(grid_for(G)), dim3(256), 0, S, sidx.as<uint64_t>(), seg.as<uint32_t>(), gc, G,
-                       segsum.as<unsigned long long>());
-    GHIP(hipGetLastError());
-    hipLaunchKernelGGL(mi_scatter, dim3(grid_for(G)), dim3(256), 0, S, sidx.as<uint64_t>(), seg.as<uint32_t>(),
-                       segsum.as<unsigned long long>(), G, (c == 0 ? px : py).as<int64_t>());
-    GHIP(hipGetLastError());
+    DQ_HIP(prim::sort_pairs(c == 0 ? xk : yk, sk, idx, sidx, 8, G, 0, 64, false, tmp, tb, S));
+    hipLaunchKernelGGL(mi_heads, dim3(grid_for(G)), dim3(256), 0, S, sk, sidx, rep, G, d_chunks, c, head, coll);
+    DQ_HIP(hipGetLastError());
+    DQ_HIP(prim::inclusive_sum_u32(head, seg, G, tmp, S));
+    DQ_HIP(hipMemsetAsync(segsum, 0, G * 8, S));
+    hipLaunchKernelGGL(mi_segsum, dim3(grid_for(G)), dim3(256), 0, S, sidx, seg, gc, G, segsum);
+    DQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(mi_scatter, dim3(grid_for(G)), dim3(256), 0, S, sidx, seg, segsum, G, c == 0 ? px : py);
+    DQ_HIP(hipGetLastError());
   }
   const int nb = (int)std::min<int64_t>(kSumBlocks, (G + 255) / 256);
-  hipLaunchKernelGGL(mi_part, dim3(nb), dim3(256), 0, S, gc, px.as<int64_t>(), py.as<int64_t>(), G, mi.total,
-                     part.as<double>());
-  GHIP(hipGetLastError());
-  hipLaunchKernelGGL(mi_final, dim3(1), dim3(64), 0, S, part.as<double>(), nb, res.as<double>());
-  GHIP(hipGetLastError());
+  hipLaunchKernelGGL(mi_part, dim3(nb), dim3(256), 0, S, gc, px, py, G, mi.total, part);
+  DQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(mi_final, dim3(1), dim3(64), 0, S, part, nb, res);
+  DQ_HIP(hipGetLastError());
   int32_t collided = 0;
-  GHIP(hipMemcpyAsync(&collided, coll.p, 4, hipMemcpyDeviceToHost, S));
-  GHIP(hipMemcpyAsync(mi.value, res.p, 8, hipMemcpyDeviceToHost, S));
-  GHIP(hipStreamSynchronize(S));
+  DQ_HIP(hipMemcpyAsync(&collided, coll, 4, hipMemcpyDeviceToHost, S));
+  if (dq_status s = read_back(mi.value, res, S)) return s;
   if (collided) return set_error(DQ_E_UNSUPPORTED, "dq_mutual_information: 64-bit key collision between distinct values");
   *mi.defined = 1;
   return DQ_OK;
 }
 
-static dq_status mi_from_joint(dq_freq_table* t, const uint64_t* sorted_keys, const uint64_t* sorted_rows, int64_t nv,
-                               const GroupCols* d_chunks, const MiRequest& mi) {
+static dq_status mi_from_joint(Frame& fr, dq_freq_table* t, const uint64_t* sorted_keys, const uint64_t* sorted_rows,
+                               int64_t nv, const GroupCols* d_chunks, const MiRequest& mi) {
   *mi.defined = 0;
   *mi.value = 0.0;
   if (nv == 0) return DQ_OK;  // sum over an empty join is NULL -> metricFromEmpty
-  const int D = t->device;
   const hipStream_t S = t->stream;
-  DevBuf gk(D, 30), gc(D, 31), nruns(D, 32), starts(D, 33), rep(D, 34), xk(D, 35), yk(D, 36), idx(D, 37), tmp(D, 45);
-  for (DevBuf* b : {&gk, &gc, &starts, &rep, &xk, &yk, &idx})
-    if (dq_status s = b->alloc(nv * 8)) return s;
-  if (dq_status s = nruns.alloc(8)) return s;
-  // (sized for the marginals' sorts and scans over at most nv groups as well: mi_from_groups does not grow it)
-  const size_t tb = std::max({prim::runs_temp_bytes(nv), prim::sort_temp_bytes(nv, 8), prim::scan_temp_bytes(nv)});
-  if (dq_status s = tmp.alloc(tb)) return s;
+  uint64_t *gk = nullptr, *rep = nullptr, *xk = nullptr, *yk = nullptr, *idx = nullptr;
+  int64_t *gc = nullptr, *starts = nullptr, *nruns = nullptr;
+  void* tmp = nullptr;  // for the runs here and, over G <= nv groups, the marginals' sorts and scans
+  if (dq_status s = take_each(fr, nv, gk, gc, starts, rep, xk, yk, idx)) return s;
+  if (dq_status s = take(fr, nruns, 1)) return s;
+  if (dq_status s = take(fr, tmp, mi_temp_bytes(nv))) return s;
   // joint groups: keys, counts and first positions of the runs of the sorted joint keys
-  GHIP(prim::runs(sorted_keys, nv, gk.as<uint64_t>(), starts.as<int64_t>(), gc.as<int64_t>(), nruns.as<int64_t>(), tmp.p, S));
+  DQ_HIP(prim::runs(sorted_keys, nv, gk, starts, gc, nruns, tmp, S));
   int64_t G = 0;
-  GHIP(hipMemcpyAsync(&G, nruns.p, 8, hipMemcpyDeviceToHost, S));
-  GHIP(hipStreamSynchronize(S));
-  hipLaunchKernelGGL(mi_group_keys, dim3(grid_for(G)), dim3(256), 0, S, sorted_rows, starts.as<int64_t>(), G, d_chunks,
-                     rep.as<uint64_t>(), xk.as<uint64_t>(), yk.as<uint64_t>(), idx.as<uint64_t>());
-  GHIP(hipGetLastError());
-  return mi_from_groups(D, S, G, gc.as<int64_t>(), rep.as<uint64_t>(), xk.as<uint64_t>(), yk.as<uint64_t>(),
-                        idx.as<uint64_t>(), d_chunks, mi);
+  if (dq_status s = read_back(&G, nruns, S)) return s;
+  hipLaunchKernelGGL(mi_group_keys, dim3(grid_for(G)), dim3(256), 0, S, sorted_rows, starts, G, d_chunks, rep, xk, yk, idx);
+  DQ_HIP(hipGetLastError());
+  return mi_from_groups(fr, S, G, gc, rep, xk, yk, idx, d_chunks, tmp, mi);
 }
 
 dq_status dq_freq_build(const int32_t* types, int32_t n_cols, const dq_column_view* cols, const int64_t* chunk_rows,
@@ -1245,7 +1215,7 @@ dq_status dq_freq_merge(const dq_freq_table* a, const dq_freq_table* b, dq_freq_
     return set_error(DQ_E_UNSUPPORTED, "dq_freq_merge: %lld groups in the two tables (at most 2^31 - 1)", (long long)n);
   if (a->hashed && ((a->n_groups > 0 && !a->d_keys2) || (b->n_groups > 0 && !b->d_keys2)))
     return set_error(DQ_E_STATE, "dq_freq_merge: hashed table without its verification hashes");
-  GHIP(hipSetDevice(a->device));
+  DQ_HIP(hipSetDevice(a->device));
   auto* t = new dq_freq_table();
   std::unique_ptr<dq_freq_table> guard(t);
   t->device = a->device;
@@ -1253,129 +1223,123 @@ dq_status dq_freq_merge(const dq_freq_table* a, const dq_freq_table* b, dq_freq_
   t->types = a->types;
   t->hashed = a->hashed;
   t->n_values = a->n_values + b->n_values;
-  std::lock_guard<std::mutex> lock(g_arena_mu);
-  const int D = a->device;
-  DevBuf k_in(D, 10), c_in(D, 11), k_s(D, 12), c_s(D, 13), nruns(D, 14), tmp(D, 15), k2_in(D, 16), pos(D, 17),
-      pos_s(D, 18), k2_s(D, 19), coll(D, 23), kdrop(D, 24), d_stores(D, 60), rep_out(D, 61);
+  Frame fr(g_arena, a->device);
+  const hipStream_t S = t->stream;
+  const int64_t na = a->n_groups, nb = b->n_groups;
+  uint64_t *k_in = nullptr, *k_s = nullptr, *rep_out = nullptr;
+  int64_t *c_in = nullptr, *c_s = nullptr, *nruns = nullptr;
+  GroupCols* d_stores = nullptr;
+  void *tmp = nullptr, *scan_tmp = nullptr;
   // both inputs self-contained: the output is, and equal first hashes are settled by the values; else the second hash
   // decides as before and the output carries no values
   const bool stores = t->hashed && a->has_store && b->has_store;
-  for (DevBuf* d : {&k_in, &c_in, &k_s, &c_s})
-    if (dq_status s = d->alloc(std::max<int64_t>(1, n) * 8)) return s;
-  if (dq_status s = nruns.alloc(8)) return s;
-  GHIP(hipMemcpyAsync(k_in.p, a->d_keys, a->n_groups * 8, hipMemcpyDeviceToDevice, t->stream));
-  GHIP(hipMemcpyAsync(k_in.as<uint64_t>() + a->n_groups, b->d_keys, b->n_groups * 8, hipMemcpyDeviceToDevice, t->stream));
-  GHIP(hipMemcpyAsync(c_in.p, a->d_counts, a->n_groups * 8, hipMemcpyDeviceToDevice, t->stream));
-  GHIP(hipMemcpyAsync(c_in.as<int64_t>() + a->n_groups, b->d_counts, b->n_groups * 8, hipMemcpyDeviceToDevice, t->stream));
-  GHIP(hipMalloc(&t->d_keys, std::max<int64_t>(1, n) * 8));
-  GHIP(hipMalloc(&t->d_counts, std::max<int64_t>(1, n) * 8));
-  if (t->hashed) GHIP(hipMalloc(&t->d_keys2, std::max<int64_t>(1, n) * 8));
+  if (dq_status s = take_each(fr, std::max<int64_t>(1, n), k_in, c_in, k_s, c_s)) return s;
+  if (dq_status s = take(fr, nruns, 1)) return s;
+  DQ_HIP(hipMemcpyAsync(k_in, a->d_keys.get(), na * 8, hipMemcpyDeviceToDevice, S));
+  DQ_HIP(hipMemcpyAsync(k_in + na, b->d_keys.get(), nb * 8, hipMemcpyDeviceToDevice, S));
+  DQ_HIP(hipMemcpyAsync(c_in, a->d_counts.get(), na * 8, hipMemcpyDeviceToDevice, S));
+  DQ_HIP(hipMemcpyAsync(c_in + na, b->d_counts.get(), nb * 8, hipMemcpyDeviceToDevice, S));
+  DQ_HIP(t->d_keys.alloc(std::max<int64_t>(1, n)));
+  DQ_HIP(t->d_counts.alloc(std::max<int64_t>(1, n)));
+  if (t->hashed) DQ_HIP(t->d_keys2.alloc(std::max<int64_t>(1, n)));
+  const size_t tb = std::max({prim::sort_temp_bytes(n, 8), prim::runs_temp_bytes(n), prim::run_sums_temp_bytes(n)});
   if (n > 0 && !t->hashed) {
     // both tables' keys are sorted: every key lies between the smaller first and the larger last key, and so
     // shares their common high bits -- the sort covers only the bits below (same order as all 64)
     uint64_t ends[4] = {~0ull, 0ull, ~0ull, 0ull};
-    if (a->n_groups > 0) {
-      GHIP(hipMemcpyAsync(&ends[0], a->d_keys, 8, hipMemcpyDeviceToHost, t->stream));
-      GHIP(hipMemcpyAsync(&ends[1], a->d_keys + (a->n_groups - 1), 8, hipMemcpyDeviceToHost, t->stream));
+    if (na > 0) {
+      DQ_HIP(hipMemcpyAsync(&ends[0], a->d_keys.get(), 8, hipMemcpyDeviceToHost, S));
+      DQ_HIP(hipMemcpyAsync(&ends[1], a->d_keys.get() + (na - 1), 8, hipMemcpyDeviceToHost, S));
     }
-    if (b->n_groups > 0) {
-      GHIP(hipMemcpyAsync(&ends[2], b->d_keys, 8, hipMemcpyDeviceToHost, t->stream));
-      GHIP(hipMemcpyAsync(&ends[3], b->d_keys + (b->n_groups - 1), 8, hipMemcpyDeviceToHost, t->stream));
+    if (nb > 0) {
+      DQ_HIP(hipMemcpyAsync(&ends[2], b->d_keys.get(), 8, hipMemcpyDeviceToHost, S));
+      DQ_HIP(hipMemcpyAsync(&ends[3], b->d_keys.get() + (nb - 1), 8, hipMemcpyDeviceToHost, S));
     }
-    GHIP(hipStreamSynchronize(t->stream));
+    DQ_HIP(hipStreamSynchronize(S));
     const uint64_t lo = std::min(ends[0], ends[2]), hi = std::max(ends[1], ends[3]);
     const int end_bit = (lo ^ hi) ? 64 - __builtin_clzll(lo ^ hi) : 1;
-    const size_t tb = std::max({prim::sort_temp_bytes(n, 8), prim::runs_temp_bytes(n), prim::run_sums_temp_bytes(n)});
-    if (dq_status s = tmp.alloc(tb)) return s;
-    if (dq_status s = pos.alloc(n * 8)) return s;  // the runs' starts
-    GHIP(prim::sort_pairs(k_in.as<uint64_t>(), k_s.as<uint64_t>(), c_in.as<int64_t>(), c_s.as<int64_t>(), 8, n, 0,
-                          end_bit, false, tmp.p, tb, t->stream));
+    int64_t* starts = nullptr;  // the runs' starts
+    if (dq_status s = take(fr, tmp, tb)) return s;
+    if (dq_status s = take(fr, starts, n)) return s;
+    DQ_HIP(prim::sort_pairs(k_in, k_s, c_in, c_s, 8, n, 0, end_bit, false, tmp, tb, S));
     // equal keys of the two tables are now neighbours: one group each, counts added
-    GHIP(prim::runs(k_s.as<uint64_t>(), n, t->d_keys, pos.as<int64_t>(), nullptr, nruns.as<int64_t>(), tmp.p, t->stream));
-    GHIP(prim::run_sums_i64(c_s.as<int64_t>(), n, pos.as<int64_t>(), nruns.as<int64_t>(), t->d_counts, tmp.p, t->stream));
-    GHIP(hipMemcpyAsync(&t->n_groups, nruns.p, 8, hipMemcpyDeviceToHost, t->stream));
+    DQ_HIP(prim::runs(k_s, n, t->d_keys.get(), starts, nullptr, nruns, tmp, S));
+    DQ_HIP(prim::run_sums_i64(c_s, n, starts, nruns, t->d_counts.get(), tmp, S));
+    DQ_HIP(hipMemcpyAsync(&t->n_groups, nruns, 8, hipMemcpyDeviceToHost, S));  // (synchronised below)
   } else if (n > 0) {
     // hashed keys: sort by the first hash carrying positions, gather (second hash, count), refuse equal first
     // hashes with different second hashes, then reduce counts and keep each group's second hash
-    for (DevBuf* d : {&k2_in, &pos, &pos_s, &k2_s, &kdrop})
-      if (dq_status s = d->alloc(n * 8)) return s;
-    if (dq_status s = coll.alloc(8)) return s;
-    GHIP(hipMemcpyAsync(k2_in.p, a->d_keys2, a->n_groups * 8, hipMemcpyDeviceToDevice, t->stream));
-    GHIP(hipMemcpyAsync(k2_in.as<uint64_t>() + a->n_groups, b->d_keys2, b->n_groups * 8, hipMemcpyDeviceToDevice,
-                        t->stream));
-    hipLaunchKernelGGL(iota_u64, dim3(grid_for(n)), dim3(256), 0, t->stream, pos.as<uint64_t>(), n);
-    GHIP(hipGetLastError());
-    const size_t tb = std::max({prim::sort_temp_bytes(n, 8), prim::runs_temp_bytes(n), prim::run_sums_temp_bytes(n)});
-    if (dq_status s = tmp.alloc(tb)) return s;
-    GHIP(prim::sort_pairs(k_in.as<uint64_t>(), k_s.as<uint64_t>(), pos.as<uint64_t>(), pos_s.as<uint64_t>(), 8, n, 0, 64,
-                          false, tmp.p, tb, t->stream));
-    GHIP(hipMemsetAsync(coll.p, 0, 8, t->stream));
+    uint64_t *k2_in = nullptr, *pos = nullptr, *pos_s = nullptr, *k2_s = nullptr;
+    int64_t* kdrop = nullptr;
+    int32_t* coll = nullptr;
+    if (dq_status s = take_each(fr, n, k2_in, pos, pos_s, k2_s, kdrop)) return s;
+    if (dq_status s = take(fr, coll, 2)) return s;
+    DQ_HIP(hipMemcpyAsync(k2_in, a->d_keys2.get(), na * 8, hipMemcpyDeviceToDevice, S));
+    DQ_HIP(hipMemcpyAsync(k2_in + na, b->d_keys2.get(), nb * 8, hipMemcpyDeviceToDevice, S));
+    hipLaunchKernelGGL(iota_u64, dim3(grid_for(n)), dim3(256), 0, S, pos, n);
+    DQ_HIP(hipGetLastError());
+    if (dq_status s = take(fr, tmp, tb)) return s;
+    DQ_HIP(prim::sort_pairs(k_in, k_s, pos, pos_s, 8, n, 0, 64, false, tmp, tb, S));
+    DQ_HIP(hipMemsetAsync(coll, 0, 8, S));
     if (stores) {  // members of a run compared exactly, value by value, through the two stores
       const GroupCols two[2] = {store_cols(a), store_cols(b)};
-      if (dq_status s = d_stores.alloc(sizeof(two))) return s;
-      GHIP(hipMemcpyAsync(d_stores.p, two, sizeof(two), hipMemcpyHostToDevice, t->stream));
-      GHIP(hipStreamSynchronize(t->stream));  // (two is on this frame)
-      hipLaunchKernelGGL(merge_gather_check_values, dim3(grid_for(n)), dim3(256), 0, t->stream, k_s.as<uint64_t>(),
-                         pos_s.as<uint64_t>(), k2_in.as<uint64_t>(), c_in.as<int64_t>(), n, a->n_groups,
-                         d_stores.as<GroupCols>(), k2_s.as<uint64_t>(), c_s.as<int64_t>(), coll.as<int32_t>());
+      if (dq_status s = take(fr, d_stores, 2)) return s;
+      DQ_HIP(hipMemcpyAsync(d_stores, two, sizeof(two), hipMemcpyHostToDevice, S));
+      DQ_HIP(hipStreamSynchronize(S));  // (two is on this frame)
+      hipLaunchKernelGGL(merge_gather_check_values, dim3(grid_for(n)), dim3(256), 0, S, k_s, pos_s, k2_in, c_in, n, na,
+                         d_stores, k2_s, c_s, coll);
     } else {
-      hipLaunchKernelGGL(merge_gather_check, dim3(grid_for(n)), dim3(256), 0, t->stream, k_s.as<uint64_t>(),
-                         pos_s.as<uint64_t>(), k2_in.as<uint64_t>(), c_in.as<int64_t>(), n, k2_s.as<uint64_t>(),
-                         c_s.as<int64_t>(), coll.as<int32_t>());
+      hipLaunchKernelGGL(merge_gather_check, dim3(grid_for(n)), dim3(256), 0, S, k_s, pos_s, k2_in, c_in, n, k2_s, c_s,
+                         coll);
     }
-    GHIP(hipGetLastError());
+    DQ_HIP(hipGetLastError());
     // runs of equal first hashes (kdrop: their starts): counts added, the first second hash kept
-    GHIP(prim::runs(k_s.as<uint64_t>(), n, t->d_keys, kdrop.as<int64_t>(), nullptr, nruns.as<int64_t>(), tmp.p, t->stream));
-    GHIP(prim::run_sums_i64(c_s.as<int64_t>(), n, kdrop.as<int64_t>(), nruns.as<int64_t>(), t->d_counts, tmp.p, t->stream));
-    GHIP(prim::run_firsts_u64(k2_s.as<uint64_t>(), n, kdrop.as<int64_t>(), nruns.as<int64_t>(), t->d_keys2, t->stream));
+    DQ_HIP(prim::runs(k_s, n, t->d_keys.get(), kdrop, nullptr, nruns, tmp, S));
+    DQ_HIP(prim::run_sums_i64(c_s, n, kdrop, nruns, t->d_counts.get(), tmp, S));
+    DQ_HIP(prim::run_firsts_u64(k2_s, n, kdrop, nruns, t->d_keys2.get(), S));
     int32_t collided = 0;
-    GHIP(hipMemcpyAsync(&collided, coll.p, 4, hipMemcpyDeviceToHost, t->stream));
-    GHIP(hipMemcpyAsync(&t->n_groups, nruns.p, 8, hipMemcpyDeviceToHost, t->stream));
-    GHIP(hipStreamSynchronize(t->stream));
+    DQ_HIP(hipMemcpyAsync(&collided, coll, 4, hipMemcpyDeviceToHost, S));
+    if (dq_status s = read_back(&t->n_groups, nruns, S)) return s;
     if (collided)
       return set_error(DQ_E_UNSUPPORTED, "dq_freq_merge: 64-bit tuple-hash collision between distinct values of the two tables");
     if (stores) {
       // every output group's tuple from the first member of its run, gathered from the two stores
-      if (dq_status s = rep_out.alloc(std::max<int64_t>(1, t->n_groups) * 8)) return s;
-      GHIP(prim::run_firsts_u64(pos_s.as<uint64_t>(), n, kdrop.as<int64_t>(), nruns.as<int64_t>(), rep_out.as<uint64_t>(),
-                                t->stream));
-      hipLaunchKernelGGL(merge_row_ids, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, rep_out.as<uint64_t>(),
-                         t->n_groups, a->n_groups);
-      GHIP(hipGetLastError());
+      if (dq_status s = take(fr, rep_out, std::max<int64_t>(1, t->n_groups))) return s;
+      DQ_HIP(prim::run_firsts_u64(pos_s, n, kdrop, nruns, rep_out, S));
+      hipLaunchKernelGGL(merge_row_ids, dim3(grid_for(t->n_groups)), dim3(256), 0, S, rep_out, t->n_groups, na);
+      DQ_HIP(hipGetLastError());
     }
   }
   if (stores) {
+    if (dq_status s = take(fr, scan_tmp, prim::scan_temp_bytes(t->n_groups + 1))) return s;
     for (int c = 0; c < (int)t->types.size(); ++c)
-      if (dq_status s = gather_column(D, t->stream, d_stores.as<GroupCols>(), rep_out.as<uint64_t>(), t->n_groups, c,
-                                      t->types[c], &t->store[c]))
-        return s;
+      if (dq_status s = gather_column(S, d_stores, rep_out, t->n_groups, c, t->types[c], scan_tmp, &t->store[c])) return s;
     t->has_store = true;
   }
-  GHIP(hipStreamSynchronize(t->stream));
+  DQ_HIP(hipStreamSynchronize(S));
   *out = guard.release();
   return DQ_OK;
 }
 
 dq_status dq_freq_summarize(const dq_freq_table* t, int64_t num_rows, dq_freq_summary* out) {
   if (!t || !out) return set_error(DQ_E_INVALID, "dq_freq_summarize: NULL argument");
-  GHIP(hipSetDevice(t->device));
+  DQ_HIP(hipSetDevice(t->device));
   std::memset(out, 0, sizeof(*out));
   out->num_groups = t->n_groups;
   out->num_values = t->n_values;
   if (t->n_groups == 0) return DQ_OK;
-  std::lock_guard<std::mutex> lock(g_arena_mu);
-  DevBuf part(t->device, 16), res(t->device, 17);
-  if (dq_status s = part.alloc(kSumBlocks * sizeof(SumPart))) return s;
-  if (dq_status s = res.alloc(sizeof(SumPart))) return s;
+  Frame fr(g_arena, t->device);
+  SumPart *part = nullptr, *res = nullptr;
+  if (dq_status s = take(fr, part, kSumBlocks)) return s;
+  if (dq_status s = take(fr, res, 1)) return s;
   const int nb = (int)std::min<int64_t>(kSumBlocks, (t->n_groups + 255) / 256);
-  hipLaunchKernelGGL(summary_part, dim3(nb), dim3(256), 0, t->stream, t->d_counts, t->n_groups, (double)num_rows,
-                     part.as<SumPart>());
-  GHIP(hipGetLastError());
-  hipLaunchKernelGGL(summary_final, dim3(1), dim3(64), 0, t->stream, part.as<SumPart>(), nb, res.as<SumPart>());
-  GHIP(hipGetLastError());
+  hipLaunchKernelGGL(summary_part, dim3(nb), dim3(256), 0, t->stream, t->d_counts.get(), t->n_groups, (double)num_rows,
+                     part);
+  DQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(summary_final, dim3(1), dim3(64), 0, t->stream, part, nb, res);
+  DQ_HIP(hipGetLastError());
   SumPart h{};
-  GHIP(hipMemcpyAsync(&h, res.p, sizeof(h), hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipStreamSynchronize(t->stream));
+  if (dq_status s = read_back(&h, res, t->stream)) return s;
   out->num_unique = h.unique;
   out->entropy = h.ent;
   return DQ_OK;
@@ -1386,12 +1350,12 @@ int64_t dq_freq_num_groups(const dq_freq_table* t) { return t ? t->n_groups : -1
 dq_status dq_freq_export(const dq_freq_table* t, uint64_t* keys, int64_t* counts, int64_t cap) {
   if (!t || cap < t->n_groups || (t->n_groups > 0 && (!keys || !counts)))
     return set_error(DQ_E_INVALID, "dq_freq_export: bad arguments");
-  GHIP(hipSetDevice(t->device));
+  DQ_HIP(hipSetDevice(t->device));
   if (t->n_groups > 0) {
-    GHIP(hipMemcpyAsync(keys, t->d_keys, t->n_groups * 8, hipMemcpyDeviceToHost, t->stream));
-    GHIP(hipMemcpyAsync(counts, t->d_counts, t->n_groups * 8, hipMemcpyDeviceToHost, t->stream));
+    DQ_HIP(hipMemcpyAsync(keys, t->d_keys.get(), t->n_groups * 8, hipMemcpyDeviceToHost, t->stream));
+    DQ_HIP(hipMemcpyAsync(counts, t->d_counts.get(), t->n_groups * 8, hipMemcpyDeviceToHost, t->stream));
   }
-  GHIP(hipStreamSynchronize(t->stream));
+  DQ_HIP(hipStreamSynchronize(t->stream));
   return DQ_OK;
 }
 
@@ -1404,32 +1368,31 @@ dq_status dq_freq_top(const dq_freq_table* t, int32_t n, uint64_t* keys, int64_t
   const int32_t m = (int32_t)std::min<int64_t>(n, t->n_groups);
   *n_out = m;
   if (m == 0) return DQ_OK;
-  GHIP(hipSetDevice(t->device));
-  std::lock_guard<std::mutex> lock(g_arena_mu);
-  const int D = t->device;
+  DQ_HIP(hipSetDevice(t->device));
+  Frame fr(g_arena, t->device);
+  const hipStream_t S = t->stream;
   const int64_t G = t->n_groups;
-  DevBuf idx(D, 50), sidx(D, 51), sc(D, 52), tmp(D, 53), ok(D, 54), oc(D, 55), orp(D, 56);
-  if (dq_status s = idx.alloc(G * 4)) return s;
-  if (dq_status s = sidx.alloc(G * 4)) return s;
-  if (dq_status s = sc.alloc(G * 8)) return s;
-  for (DevBuf* b : {&ok, &oc, &orp})
-    if (dq_status s = b->alloc((size_t)m * 8)) return s;
-  hipLaunchKernelGGL(iota_u32, dim3(grid_for(G)), dim3(256), 0, t->stream, idx.as<uint32_t>(), G);
-  GHIP(hipGetLastError());
+  uint32_t *idx = nullptr, *sidx = nullptr;
+  uint64_t *sc = nullptr, *ok = nullptr, *orp = nullptr;
+  int64_t* oc = nullptr;
+  void* tmp = nullptr;
+  if (dq_status s = take_each(fr, G, idx, sidx, sc)) return s;
+  if (dq_status s = take_each(fr, m, ok, oc, orp)) return s;
+  hipLaunchKernelGGL(iota_u32, dim3(grid_for(G)), dim3(256), 0, S, idx, G);
+  DQ_HIP(hipGetLastError());
   // counts descending, ties in key order (stable radix sort over groups already in key order); every count is in
   // [1, n_values], so the bits above n_values' highest set bit are zero in all of them
   const int end_bit = t->n_values > 0 ? 64 - __builtin_clzll((unsigned long long)t->n_values) : 1;
   const size_t tb = prim::sort_temp_bytes(G, 4);
-  if (dq_status s = tmp.alloc(tb)) return s;
-  GHIP(prim::sort_pairs(reinterpret_cast<const uint64_t*>(t->d_counts), sc.as<uint64_t>(), idx.as<uint32_t>(),
-                        sidx.as<uint32_t>(), 4, G, 0, end_bit, true, tmp.p, tb, t->stream));
-  hipLaunchKernelGGL(gather_top, dim3((m + 255) / 256), dim3(256), 0, t->stream, sidx.as<uint32_t>(), m, t->d_keys,
-                     t->d_counts, t->d_rep, ok.as<uint64_t>(), oc.as<int64_t>(), orp.as<uint64_t>());
-  GHIP(hipGetLastError());
-  GHIP(hipMemcpyAsync(keys, ok.p, (size_t)m * 8, hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipMemcpyAsync(counts, oc.p, (size_t)m * 8, hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipMemcpyAsync(rep_rows, orp.p, (size_t)m * 8, hipMemcpyDeviceToHost, t->stream));
-  GHIP(hipStreamSynchronize(t->stream));
+  if (dq_status s = take(fr, tmp, tb)) return s;
+  DQ_HIP(prim::sort_pairs(t->d_counts.as<const uint64_t>(), sc, idx, sidx, 4, G, 0, end_bit, true, tmp, tb, S));
+  hipLaunchKernelGGL(gather_top, dim3((m + 255) / 256), dim3(256), 0, S, sidx, m, t->d_keys.get(), t->d_counts.get(),
+                     t->d_rep.get(), ok, oc, orp);
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(hipMemcpyAsync(keys, ok, (size_t)m * 8, hipMemcpyDeviceToHost, S));
+  DQ_HIP(hipMemcpyAsync(counts, oc, (size_t)m * 8, hipMemcpyDeviceToHost, S));
+  DQ_HIP(hipMemcpyAsync(rep_rows, orp, (size_t)m * 8, hipMemcpyDeviceToHost, S));
+  DQ_HIP(hipStreamSynchronize(S));
   return DQ_OK;
 }
 
@@ -1445,51 +1408,41 @@ dq_status dq_freq_materialize(dq_freq_table* t, const dq_column_view* cols, cons
       (t->n_groups > 0 && n_chunks == 0))
     return set_error(DQ_E_INVALID, "dq_freq_materialize: bad chunks (%d for %lld groups)", n_chunks, (long long)t->n_groups);
   std::vector<GroupCols> gcs(std::max(1, n_chunks));
-  std::memset(gcs.data(), 0, gcs.size() * sizeof(GroupCols));
   for (int k = 0; k < n_chunks; ++k) {
     if (chunk_rows[k] < 0 || chunk_rows[k] >= (1ll << kRowBits)) return set_error(DQ_E_INVALID, "chunk rows");
-    GroupCols& g = gcs[k];
-    g.n_cols = n_cols;
-    g.key_mask = ~0ull;
-    for (int c = 0; c < n_cols; ++c) {
-      const dq_column_view& v = cols[(size_t)k * n_cols + c];
-      g.values[c] = v.values;
-      g.offsets[c] = v.offsets;
-      g.type[c] = t->types[c];
-    }
+    gcs[k] = view_cols(t->types.data(), n_cols, cols + (size_t)k * n_cols, ~0ull, false);
   }
-  GHIP(hipSetDevice(t->device));
-  std::lock_guard<std::mutex> lock(g_arena_mu);
-  const int D = t->device;
-  DevBuf d_chunks(D, 60), d_rows(D, 63), bad(D, 64);
-  if (dq_status s = d_chunks.alloc(gcs.size() * sizeof(GroupCols))) return s;
-  if (dq_status s = d_rows.alloc(std::max(1, n_chunks) * 8)) return s;
-  if (dq_status s = bad.alloc(8)) return s;
-  GHIP(hipMemcpyAsync(d_chunks.p, gcs.data(), gcs.size() * sizeof(GroupCols), hipMemcpyHostToDevice, t->stream));
+  DQ_HIP(hipSetDevice(t->device));
+  Frame fr(g_arena, t->device);
+  const hipStream_t S = t->stream;
+  GroupCols* d_chunks = nullptr;
+  int64_t* d_rows = nullptr;
+  int32_t* bad = nullptr;
+  void* scan_tmp = nullptr;
+  if (dq_status s = take(fr, d_chunks, gcs.size())) return s;
+  if (dq_status s = take(fr, d_rows, std::max(1, n_chunks))) return s;
+  if (dq_status s = take(fr, bad, 2)) return s;
+  if (dq_status s = take(fr, scan_tmp, prim::scan_temp_bytes(t->n_groups + 1))) return s;
+  DQ_HIP(hipMemcpyAsync(d_chunks, gcs.data(), gcs.size() * sizeof(GroupCols), hipMemcpyHostToDevice, S));
   if (t->n_groups > 0) {
     // the views must cover every stored row id before anything is read through them
-    GHIP(hipMemcpyAsync(d_rows.p, chunk_rows, (size_t)n_chunks * 8, hipMemcpyHostToDevice, t->stream));
-    GHIP(hipMemsetAsync(bad.p, 0, 8, t->stream));
-    hipLaunchKernelGGL(rep_check, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, t->d_rep, t->n_groups,
-                       d_rows.as<int64_t>(), n_chunks, bad.as<int32_t>());
-    GHIP(hipGetLastError());
+    DQ_HIP(hipMemcpyAsync(d_rows, chunk_rows, (size_t)n_chunks * 8, hipMemcpyHostToDevice, S));
     int32_t out_of_range = 0;
-    GHIP(hipMemcpyAsync(&out_of_range, bad.p, 4, hipMemcpyDeviceToHost, t->stream));
-    GHIP(hipStreamSynchronize(t->stream));
+    if (dq_status s = read_flag(bad, S, &out_of_range, [&] {
+          hipLaunchKernelGGL(rep_check, dim3(grid_for(t->n_groups)), dim3(256), 0, S, t->d_rep.get(), t->n_groups, d_rows,
+                             n_chunks, bad);
+        }))
+      return s;
     if (out_of_range)
       return set_error(DQ_E_INVALID, "dq_freq_materialize: the chunks do not cover the table's representative rows "
                                      "(not the views it was built from)");
   }
   StoreCol cols_out[kMaxGroupCols];
   for (int c = 0; c < n_cols; ++c)
-    if (dq_status s = gather_column(D, t->stream, d_chunks.as<GroupCols>(), t->d_rep, t->n_groups, c, t->types[c], &cols_out[c]))
+    if (dq_status s = gather_column(S, d_chunks, t->d_rep.get(), t->n_groups, c, t->types[c], scan_tmp, &cols_out[c]))
       return s;
-  GHIP(hipStreamSynchronize(t->stream));
-  for (int c = 0; c < n_cols; ++c) {  // all columns or none
-    std::swap(t->store[c].values, cols_out[c].values);
-    std::swap(t->store[c].offsets, cols_out[c].offsets);
-    t->store[c].bytes = cols_out[c].bytes;
-  }
+  DQ_HIP(hipStreamSynchronize(S));
+  for (int c = 0; c < n_cols; ++c) t->store[c] = std::move(cols_out[c]);  // all columns or none
   t->has_store = true;
   return DQ_OK;
 }
@@ -1527,7 +1480,7 @@ int64_t dq_freq_to_bytes(const dq_freq_table* t, uint8_t* out, int64_t cap) {
   FreqImageView v;
   const int64_t size = image_layout(t, &v);
   if (!out || cap < size) return size;
-  GHIP(hipSetDevice(t->device));
+  DQ_HIP(hipSetDevice(t->device));
   std::memset(out, 0, (size_t)size);
   std::memcpy(out, "DQFT", 4);
   const uint32_t head[3] = {kFreqImageVersion, kFreqImageOrder, (uint32_t)v.n_cols};
@@ -1541,19 +1494,19 @@ int64_t dq_freq_to_bytes(const dq_freq_table* t, uint8_t* out, int64_t cap) {
   const int64_t G = v.n_groups;
   const hipStream_t S = t->stream;
   if (G > 0) {
-    GHIP(hipMemcpyAsync(out + v.keys, t->d_keys, G * 8, hipMemcpyDeviceToHost, S));
-    GHIP(hipMemcpyAsync(out + v.counts, t->d_counts, G * 8, hipMemcpyDeviceToHost, S));
-    if (t->hashed) GHIP(hipMemcpyAsync(out + v.keys2, t->d_keys2, G * 8, hipMemcpyDeviceToHost, S));
+    DQ_HIP(hipMemcpyAsync(out + v.keys, t->d_keys.get(), G * 8, hipMemcpyDeviceToHost, S));
+    DQ_HIP(hipMemcpyAsync(out + v.counts, t->d_counts.get(), G * 8, hipMemcpyDeviceToHost, S));
+    if (t->hashed) DQ_HIP(hipMemcpyAsync(out + v.keys2, t->d_keys2.get(), G * 8, hipMemcpyDeviceToHost, S));
   }
   for (int c = 0; c < v.n_cols && t->hashed; ++c) {
     if (v.col_offsets[c]) {
       std::memcpy(out + v.col_offsets[c] - 8, &v.col_bytes[c], 8);
-      GHIP(hipMemcpyAsync(out + v.col_offsets[c], t->store[c].offsets, (G + 1) * 8, hipMemcpyDeviceToHost, S));
+      DQ_HIP(hipMemcpyAsync(out + v.col_offsets[c], t->store[c].offsets.get(), (G + 1) * 8, hipMemcpyDeviceToHost, S));
     }
     if (v.col_bytes[c] > 0)
-      GHIP(hipMemcpyAsync(out + v.col_values[c], t->store[c].values, v.col_bytes[c], hipMemcpyDeviceToHost, S));
+      DQ_HIP(hipMemcpyAsync(out + v.col_values[c], t->store[c].values.get(), v.col_bytes[c], hipMemcpyDeviceToHost, S));
   }
-  GHIP(hipStreamSynchronize(S));
+  DQ_HIP(hipStreamSynchronize(S));
   return size;
 }
 
@@ -1563,7 +1516,7 @@ dq_status dq_freq_from_bytes(const uint8_t* bytes, int64_t n, int32_t device, vo
   FreqImageView v;
   char err[256];
   if (dq_status s = freq_image_parse(bytes, n, &v, err, sizeof(err))) return set_error(s, "%s", err);
-  GHIP(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   auto* t = new dq_freq_table();
   std::unique_ptr<dq_freq_table> guard(t);
   t->device = device;
@@ -1574,26 +1527,26 @@ dq_status dq_freq_from_bytes(const uint8_t* bytes, int64_t n, int32_t device, vo
   t->n_values = v.n_values;
   const int64_t G = v.n_groups;
   const hipStream_t S = t->stream;
-  GHIP(hipMalloc(&t->d_keys, std::max<int64_t>(1, G) * 8));
-  GHIP(hipMalloc(&t->d_counts, std::max<int64_t>(1, G) * 8));
-  if (t->hashed) GHIP(hipMalloc(&t->d_keys2, std::max<int64_t>(1, G) * 8));
+  DQ_HIP(t->d_keys.alloc(std::max<int64_t>(1, G)));
+  DQ_HIP(t->d_counts.alloc(std::max<int64_t>(1, G)));
+  if (t->hashed) DQ_HIP(t->d_keys2.alloc(std::max<int64_t>(1, G)));
   if (G > 0) {
-    GHIP(hipMemcpyAsync(t->d_keys, bytes + v.keys, G * 8, hipMemcpyHostToDevice, S));
-    GHIP(hipMemcpyAsync(t->d_counts, bytes + v.counts, G * 8, hipMemcpyHostToDevice, S));
-    if (t->hashed) GHIP(hipMemcpyAsync(t->d_keys2, bytes + v.keys2, G * 8, hipMemcpyHostToDevice, S));
+    DQ_HIP(hipMemcpyAsync(t->d_keys.get(), bytes + v.keys, G * 8, hipMemcpyHostToDevice, S));
+    DQ_HIP(hipMemcpyAsync(t->d_counts.get(), bytes + v.counts, G * 8, hipMemcpyHostToDevice, S));
+    if (t->hashed) DQ_HIP(hipMemcpyAsync(t->d_keys2.get(), bytes + v.keys2, G * 8, hipMemcpyHostToDevice, S));
   }
   for (int c = 0; c < v.n_cols && t->hashed; ++c) {
     StoreCol& sc = t->store[c];
     sc.bytes = v.col_bytes[c];
-    GHIP(hipMalloc(&sc.values, std::max<int64_t>(8, sc.bytes)));
-    if (sc.bytes > 0) GHIP(hipMemcpyAsync(sc.values, bytes + v.col_values[c], sc.bytes, hipMemcpyHostToDevice, S));
+    DQ_HIP(sc.values.alloc(std::max<int64_t>(8, sc.bytes)));
+    if (sc.bytes > 0) DQ_HIP(hipMemcpyAsync(sc.values.get(), bytes + v.col_values[c], sc.bytes, hipMemcpyHostToDevice, S));
     if (v.col_offsets[c]) {
-      GHIP(hipMalloc(&sc.offsets, (G + 1) * 8));
-      GHIP(hipMemcpyAsync(sc.offsets, bytes + v.col_offsets[c], (G + 1) * 8, hipMemcpyHostToDevice, S));
+      DQ_HIP(sc.offsets.alloc(G + 1));
+      DQ_HIP(hipMemcpyAsync(sc.offsets.get(), bytes + v.col_offsets[c], (G + 1) * 8, hipMemcpyHostToDevice, S));
     }
   }
   t->has_store = t->hashed != 0;
-  GHIP(hipStreamSynchronize(S));
+  DQ_HIP(hipStreamSynchronize(S));
   *out = guard.release();
   return DQ_OK;
 }
@@ -1607,25 +1560,25 @@ dq_status dq_freq_mutual_information(const dq_freq_table* t, int64_t num_rows, d
   *value = 0.0;
   const int64_t G = t->n_groups;
   if (G == 0) return DQ_OK;  // sum over an empty join is NULL -> metricFromEmpty
-  GHIP(hipSetDevice(t->device));
-  std::lock_guard<std::mutex> lock(g_arena_mu);
-  const int D = t->device;
+  DQ_HIP(hipSetDevice(t->device));
+  Frame fr(g_arena, t->device);
   const hipStream_t S = t->stream;
-  DevBuf rep(D, 34), xk(D, 35), yk(D, 36), d_store(D, 60);
-  for (DevBuf* b : {&rep, &xk, &yk})
-    if (dq_status s = b->alloc(G * 8)) return s;
-  if (dq_status s = d_store.alloc(sizeof(GroupCols))) return s;
+  uint64_t *rep = nullptr, *xk = nullptr, *yk = nullptr;
+  GroupCols* d_store = nullptr;
+  void* tmp = nullptr;
+  if (dq_status s = take_each(fr, G, rep, xk, yk)) return s;
+  if (dq_status s = take(fr, d_store, 1)) return s;
+  if (dq_status s = take(fr, tmp, mi_temp_bytes(G))) return s;
   const GroupCols st = store_cols(t);
-  GHIP(hipMemcpyAsync(d_store.p, &st, sizeof(st), hipMemcpyHostToDevice, S));
-  GHIP(hipStreamSynchronize(S));
+  DQ_HIP(hipMemcpyAsync(d_store, &st, sizeof(st), hipMemcpyHostToDevice, S));
+  DQ_HIP(hipStreamSynchronize(S));
   // group g is row g of the store: its row id and its index are both g
-  hipLaunchKernelGGL(iota_u64, dim3(grid_for(G)), dim3(256), 0, S, rep.as<uint64_t>(), G);
-  GHIP(hipGetLastError());
-  hipLaunchKernelGGL(store_col_keys, dim3(grid_for(G)), dim3(256), 0, S, st, G, xk.as<uint64_t>(), yk.as<uint64_t>());
-  GHIP(hipGetLastError());
+  hipLaunchKernelGGL(iota_u64, dim3(grid_for(G)), dim3(256), 0, S, rep, G);
+  DQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(store_col_keys, dim3(grid_for(G)), dim3(256), 0, S, st, G, xk, yk);
+  DQ_HIP(hipGetLastError());
   const MiRequest mi{(double)num_rows, value, defined};
-  return mi_from_groups(D, S, G, t->d_counts, rep.as<uint64_t>(), xk.as<uint64_t>(), yk.as<uint64_t>(), rep.as<uint64_t>(),
-                        d_store.as<GroupCols>(), mi);
+  return mi_from_groups(fr, S, G, t->d_counts.get(), rep, xk, yk, rep, d_store, tmp, mi);
 }
 
 dq_status dq_freq_take_values(const dq_freq_table* t, const uint64_t* keys, int32_t n, int32_t col, void* values,
@@ -1635,36 +1588,37 @@ dq_status dq_freq_take_values(const dq_freq_table* t, const uint64_t* keys, int3
   if (!t->has_store) return set_error(DQ_E_STATE, "dq_freq_take_values: the table does not own its values");
   const int es = dq_freq_elem_size(t->types[col]);
   if (es == 0 && !offsets) return set_error(DQ_E_INVALID, "dq_freq_take_values: a string column needs offsets[n + 1]");
-  GHIP(hipSetDevice(t->device));
-  std::lock_guard<std::mutex> lock(g_arena_mu);
-  const int D = t->device;
+  DQ_HIP(hipSetDevice(t->device));
+  Frame fr(g_arena, t->device);
   const hipStream_t S = t->stream;
-  DevBuf want(D, 65), idx(D, 66), missing(D, 64), d_store(D, 60);
-  for (DevBuf* b : {&want, &idx})
-    if (dq_status s = b->alloc(std::max(1, n) * 8)) return s;
-  if (dq_status s = missing.alloc(8)) return s;
-  if (dq_status s = d_store.alloc(sizeof(GroupCols))) return s;
+  uint64_t *want = nullptr, *idx = nullptr;
+  int32_t* missing = nullptr;
+  GroupCols* d_store = nullptr;
+  void* scan_tmp = nullptr;
+  if (dq_status s = take_each(fr, std::max(1, n), want, idx)) return s;
+  if (dq_status s = take(fr, missing, 2)) return s;
+  if (dq_status s = take(fr, d_store, 1)) return s;
+  if (dq_status s = take(fr, scan_tmp, prim::scan_temp_bytes((int64_t)n + 1))) return s;
   const GroupCols st = store_cols(t);
-  GHIP(hipMemcpyAsync(d_store.p, &st, sizeof(st), hipMemcpyHostToDevice, S));
+  DQ_HIP(hipMemcpyAsync(d_store, &st, sizeof(st), hipMemcpyHostToDevice, S));
   if (n > 0) {
-    GHIP(hipMemcpyAsync(want.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, S));
-    GHIP(hipMemsetAsync(missing.p, 0, 8, S));
-    hipLaunchKernelGGL(find_groups, dim3((n + 255) / 256), dim3(256), 0, S, want.as<uint64_t>(), n, t->d_keys, t->n_groups,
-                       idx.as<uint64_t>(), missing.as<int32_t>());
-    GHIP(hipGetLastError());
+    DQ_HIP(hipMemcpyAsync(want, keys, (size_t)n * 8, hipMemcpyHostToDevice, S));
     int32_t miss = 0;
-    GHIP(hipMemcpyAsync(&miss, missing.p, 4, hipMemcpyDeviceToHost, S));
-    GHIP(hipStreamSynchronize(S));
+    if (dq_status s = read_flag(missing, S, &miss, [&] {
+          hipLaunchKernelGGL(find_groups, dim3((n + 255) / 256), dim3(256), 0, S, want, n, t->d_keys.get(), t->n_groups, idx,
+                             missing);
+        }))
+      return s;
     if (miss) return set_error(DQ_E_INVALID, "dq_freq_take_values: a key that is not a group of the table");
   }
-  GHIP(hipStreamSynchronize(S));
+  DQ_HIP(hipStreamSynchronize(S));
   StoreCol got;
-  if (dq_status s = gather_column(D, S, d_store.as<GroupCols>(), idx.as<uint64_t>(), n, col, t->types[col], &got)) return s;
+  if (dq_status s = gather_column(S, d_store, idx, n, col, t->types[col], scan_tmp, &got)) return s;
   *values_bytes = got.bytes;
-  if (got.offsets) GHIP(hipMemcpyAsync(offsets, got.offsets, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, S));
+  if (got.offsets) DQ_HIP(hipMemcpyAsync(offsets, got.offsets.get(), ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, S));
   if (values && values_cap >= got.bytes && got.bytes > 0)
-    GHIP(hipMemcpyAsync(values, got.values, got.bytes, hipMemcpyDeviceToHost, S));
-  GHIP(hipStreamSynchronize(S));
+    DQ_HIP(hipMemcpyAsync(values, got.values.get(), got.bytes, hipMemcpyDeviceToHost, S));
+  DQ_HIP(hipStreamSynchronize(S));
   return DQ_OK;
 }
 

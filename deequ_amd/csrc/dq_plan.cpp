@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "dq_device.h"
-#include "dq_internal.h"
+#include "dq_hip_host.h"
 #include "dq_pred_jit.h"
 
 // predicate-pass workgroups per chunk (A/B builds: -DDQ_PRED_WGS=...)
@@ -96,14 +96,6 @@ static dq_status cap_error(const char* fmt, ...) {
   g_capacity = true;
   return DQ_E_UNSUPPORTED;
 }
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return set_error(e_ == hipErrorOutOfMemory ? DQ_E_OOM : DQ_E_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(e_), __FILE__, __LINE__);                          \
-  } while (0)
 
 // Preconditions.isNumeric (Analyzer.scala:322-334): ByteType .. DoubleType and DecimalType
 static bool is_numeric(int32_t t) {
@@ -740,16 +732,16 @@ struct dq_plan {
 
 static dq_status take_event(dq_plan* p, hipEvent_t* e) {
   if (!p->ev_pool.empty()) { *e = p->ev_pool.back(); p->ev_pool.pop_back(); return DQ_OK; }
-  HIP_TRY(hipEventCreate(e));
+  DQ_HIP(hipEventCreate(e));
   return DQ_OK;
 }
 
 static dq_status resolve_timing(dq_plan* p) {
   if (p->pending.empty()) return DQ_OK;
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  DQ_HIP(hipStreamSynchronize(p->stream));
   for (auto& q : p->pending) {
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, q.a, q.b));
+    DQ_HIP(hipEventElapsedTime(&ms, q.a, q.b));
     p->kernel_ms[q.kernel] += ms;
     p->kernel_launches[q.kernel] += 1;
     p->ev_pool.push_back(q.a);
@@ -766,11 +758,11 @@ static dq_status timed(dq_plan* p, int kernel, hipStream_t st, F fn) {
   if (p->timing) {
     if (dq_status s = take_event(p, &a)) return s;
     if (dq_status s = take_event(p, &b)) return s;
-    HIP_TRY(hipEventRecord(a, st));
+    DQ_HIP(hipEventRecord(a, st));
   }
-  HIP_TRY(fn());
+  DQ_HIP(fn());
   if (p->timing) {
-    HIP_TRY(hipEventRecord(b, st));
+    DQ_HIP(hipEventRecord(b, st));
     p->pending.push_back({kernel, a, b});
   }
   return DQ_OK;
@@ -798,11 +790,11 @@ static dq_status free_plan_mem(dq_plan* p) {
 }
 
 static dq_status reset_acc(dq_plan* p) {
-  HIP_TRY(launch_init_acc(p->d_col_acc, (int32_t)p->col_tasks.size(), p->d_pair_acc, (int32_t)p->pair_tasks.size(),
+  DQ_HIP(launch_init_acc(p->d_col_acc, (int32_t)p->col_tasks.size(), p->d_pair_acc, (int32_t)p->pair_tasks.size(),
                           p->d_rare_dev, p->stream));
-  if (p->n_hll) HIP_TRY(hipMemsetAsync(p->d_hll_acc, 0, (size_t)p->n_hll * kHllCopies * 512 * sizeof(uint32_t), p->stream));
-  if (p->n_hll && p->d_hll_floor) HIP_TRY(hipMemsetAsync(p->d_hll_floor, 0, (size_t)p->n_hll * sizeof(uint32_t), p->stream));
-  if (p->has_pred) HIP_TRY(hipMemsetAsync(p->d_pred_acc, 0, kPredAccCopies * sizeof(PredPartial), p->stream));
+  if (p->n_hll) DQ_HIP(hipMemsetAsync(p->d_hll_acc, 0, (size_t)p->n_hll * kHllCopies * 512 * sizeof(uint32_t), p->stream));
+  if (p->n_hll && p->d_hll_floor) DQ_HIP(hipMemsetAsync(p->d_hll_floor, 0, (size_t)p->n_hll * sizeof(uint32_t), p->stream));
+  if (p->has_pred) DQ_HIP(hipMemsetAsync(p->d_pred_acc, 0, kPredAccCopies * sizeof(PredPartial), p->stream));
   if (p->total_rows > 0) p->prev_rows = p->total_rows;
   p->total_rows = 0;
   p->next_chunk = 0;
@@ -812,7 +804,7 @@ static dq_status reset_acc(dq_plan* p) {
 template <typename T>
 static dq_status dmalloc(T** ptr, size_t bytes) {
   if (bytes == 0) bytes = 16;
-  HIP_TRY(hipMalloc((void**)ptr, bytes));
+  DQ_HIP(hipMalloc((void**)ptr, bytes));
   return DQ_OK;
 }
 
@@ -1349,7 +1341,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   if (dq_status s = dmalloc(&p->d_pair_tasks, npt * sizeof(PairTask))) return s;
   if (dq_status s = dmalloc(&p->d_pair_wgs, p->pair_wgs.size() * sizeof(PairWG))) return s;
   if (!p->pair_wgs.empty())
-    HIP_TRY(hipMemcpyAsync(p->d_pair_wgs, p->pair_wgs.data(), p->pair_wgs.size() * sizeof(PairWG),
+    DQ_HIP(hipMemcpyAsync(p->d_pair_wgs, p->pair_wgs.data(), p->pair_wgs.size() * sizeof(PairWG),
                            hipMemcpyHostToDevice, p->stream));
   if (dq_status s = dmalloc(&p->d_pair_redo, p->pair_wgs.size() * kPairWaves * kMaxWG * sizeof(int32_t))) return s;
   if (dq_status s = dmalloc(&p->d_prog, sizeof(PredProgram))) return s;
@@ -1359,7 +1351,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   if (dq_status s = dmalloc(&p->d_col_acc, nct * sizeof(ColPartial))) return s;
   // counters [0, nct) (zeroed by every reset) and the values last published to h_rare [nct, 2 nct)
   if (dq_status s = dmalloc(&p->d_rare_dev, 2 * nct * sizeof(int64_t))) return s;
-  if (nct) HIP_TRY(hipMemsetAsync(p->d_rare_dev, 0, 2 * nct * sizeof(int64_t), p->stream));
+  if (nct) DQ_HIP(hipMemsetAsync(p->d_rare_dev, 0, 2 * nct * sizeof(int64_t), p->stream));
   p->str_long.assign(nct, 0);
   if (const char* e = std::getenv("DQ_STR_PATH")) p->str_path = std::strcmp(e, "fast") == 0 ? 1 : std::strcmp(e, "long") == 0 ? 2 : 0;
   if (nct && hipHostMalloc(reinterpret_cast<void**>(&p->h_rare), nct * sizeof(int64_t), hipHostMallocMapped) == hipSuccess) {
@@ -1380,18 +1372,18 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   if (dq_status s = dmalloc(&p->d_pair_acc, npt * sizeof(CorrPartial))) return s;
   // (kPredAccCopies copies: the compiled predicate pass spreads its counter atomics over them; the host adds them)
   if (dq_status s = dmalloc(&p->d_pred_acc, kPredAccCopies * sizeof(PredPartial))) return s;
-  if (nct) HIP_TRY(hipMemcpyAsync(p->d_col_tasks, p->col_tasks.data(), nct * sizeof(ColTask), hipMemcpyHostToDevice, p->stream));
-  if (npt) HIP_TRY(hipMemcpyAsync(p->d_pair_tasks, p->pair_tasks.data(), npt * sizeof(PairTask), hipMemcpyHostToDevice, p->stream));
+  if (nct) DQ_HIP(hipMemcpyAsync(p->d_col_tasks, p->col_tasks.data(), nct * sizeof(ColTask), hipMemcpyHostToDevice, p->stream));
+  if (npt) DQ_HIP(hipMemcpyAsync(p->d_pair_tasks, p->pair_tasks.data(), npt * sizeof(PairTask), hipMemcpyHostToDevice, p->stream));
   if (!p->regex_blob.empty()) {
     if (dq_status s = dmalloc(&p->d_regex, p->regex_blob.size() * sizeof(uint16_t))) return s;
-    HIP_TRY(hipMemcpyAsync(p->d_regex, p->regex_blob.data(), p->regex_blob.size() * sizeof(uint16_t),
+    DQ_HIP(hipMemcpyAsync(p->d_regex, p->regex_blob.data(), p->regex_blob.size() * sizeof(uint16_t),
                            hipMemcpyHostToDevice, p->stream));
   }
   p->prog.regex = p->d_regex;
   p->prog.regex_words = (int32_t)p->regex_blob.size();
-  HIP_TRY(hipMemcpyAsync(p->d_prog, &p->prog, sizeof(PredProgram), hipMemcpyHostToDevice, p->stream));
+  DQ_HIP(hipMemcpyAsync(p->d_prog, &p->prog, sizeof(PredProgram), hipMemcpyHostToDevice, p->stream));
   if (dq_status s = reset_acc(p)) return s;
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  DQ_HIP(hipStreamSynchronize(p->stream));
   return DQ_OK;
 }
 
@@ -1657,9 +1649,9 @@ dq_status dq_plan_create_opts(const dq_analyzer_spec* specs, int32_t n_specs, co
     if (!type_valid(schema[c].type))
       return set_error(DQ_E_TYPE, "dq_plan_create: column %d has unknown type %d", c, schema[c].type);
   int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
+  DQ_HIP(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return set_error(DQ_E_INVALID, "dq_plan_create: device %d of %d", device, ndev);
-  HIP_TRY(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   const std::vector<dq_analyzer_spec> vspecs(specs, specs + n_specs);
   const std::vector<dq_column_desc> vschema(schema, schema + n_cols);
   std::vector<std::string> vpat;
@@ -1715,12 +1707,12 @@ dq_status dq_plan_create_opts(const dq_analyzer_spec* specs, int32_t n_specs, co
 
 dq_status dq_plan_set_stream(dq_plan* p, void* hip_stream) {
   if (!p) return set_error(DQ_E_INVALID, "dq_plan_set_stream: plan is NULL");
-  HIP_TRY(hipSetDevice(p->device));
+  DQ_HIP(hipSetDevice(p->device));
   // a composite plan's parts launch on the parent's stream (they never own one): one sync of the old stream
   // covers their work too, then every part moves to the new stream before the old one may be destroyed
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  DQ_HIP(hipStreamSynchronize(p->stream));
   for (dq_plan* q : p->parts) {
-    if (q->stream != p->stream) HIP_TRY(hipStreamSynchronize(q->stream));  // (not reachable: parts share it)
+    if (q->stream != p->stream) DQ_HIP(hipStreamSynchronize(q->stream));  // (not reachable: parts share it)
     if (q->own_stream) (void)hipStreamDestroy(q->stream);
     q->stream = (hipStream_t)hip_stream;
     q->own_stream = false;
@@ -1761,7 +1753,7 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
                      (long long)p->next_chunk);
   const int32_t ncols = (int32_t)p->schema.size();
   if (ncols > 0 && !cols) return set_error(DQ_E_INVALID, "dq_scan: cols is NULL");
-  HIP_TRY(hipSetDevice(p->device));
+  DQ_HIP(hipSetDevice(p->device));
   if (!p->parts.empty()) {  // composite: every part over its own columns of this chunk, in part order
     // every view any part reads is checked before the first part scans: a rejected view must leave every
     // part's chunk count where it was (a partly scanned chunk could not be retried, and dq_finish would
@@ -1812,7 +1804,7 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
   // where bitmaps (64 rows per word), grown on demand
   const int64_t words = ceil_div(n_rows, 64);
   if (p->prog.n_bitmaps > 0 && words > p->where_cap_words) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    DQ_HIP(hipStreamSynchronize(p->stream));
     for (int b = 0; b < p->prog.n_bitmaps; ++b) {
       if (p->d_where_bits[b]) (void)hipFree(p->d_where_bits[b]);
       p->d_where_bits[b] = nullptr;
@@ -1826,11 +1818,11 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
   // all-ones bitmap standing in for a missing validity / where bitmap in the pair pass and the compiled
   // predicate pass
   if ((!p->pair_wgs.empty() || p->pred_jit) && words + 1 > p->ones_cap_words) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    DQ_HIP(hipStreamSynchronize(p->stream));
     if (p->d_ones) (void)hipFree(p->d_ones);
     p->d_ones = nullptr;
     if (dq_status s = dmalloc(&p->d_ones, (size_t)(words + 1) * 8)) return s;
-    HIP_TRY(hipMemsetAsync(p->d_ones, 0xFF, (size_t)(words + 1) * 8, p->stream));
+    DQ_HIP(hipMemsetAsync(p->d_ones, 0xFF, (size_t)(words + 1) * 8, p->stream));
     p->ones_cap_words = words + 1;
   }
 
@@ -1916,8 +1908,8 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
     int32_t& res = p->pair_resident[pair_ring ? 1 : 0];
     if (res == 0) {
       int32_t per_cu = 0, cus = 0;
-      HIP_TRY(pair_scan_residency(p->pair_all_f64, pair_ring, p->pair_minmax, &per_cu));
-      HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
+      DQ_HIP(pair_scan_residency(p->pair_all_f64, pair_ring, p->pair_minmax, &per_cu));
+      DQ_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
       res = std::max<int32_t>(1, per_cu * cus);
     }
     const int64_t per_round = std::max<int64_t>(1, res / (int64_t)p->pair_wgs.size());
@@ -2014,7 +2006,7 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
 dq_status dq_finish(dq_plan* p, dq_state* out) {
   if (!p) return set_error(DQ_E_INVALID, "dq_finish: plan is NULL");
   if (!out && !p->specs.empty()) return set_error(DQ_E_INVALID, "dq_finish: out is NULL");
-  HIP_TRY(hipSetDevice(p->device));
+  DQ_HIP(hipSetDevice(p->device));
   if (!p->parts.empty()) {
     std::vector<dq_state> tmp;
     for (size_t k = 0; k < p->parts.size(); ++k) {
@@ -2050,11 +2042,11 @@ dq_status dq_finish(dq_plan* p, dq_state* out) {
   void* const dst_hll = hs ? (void*)(hs + o_hll) : (void*)hll.data();
   void* const dst_pair = hs ? (void*)(hs + o_pair) : (void*)pair.data();
   void* const dst_pred = hs ? (void*)(hs + o_pred) : (void*)pred_copies.data();
-  if (b_col) HIP_TRY(hipMemcpyAsync(dst_col, p->d_col_acc, b_col, hipMemcpyDeviceToHost, p->stream));
-  if (b_hll) HIP_TRY(hipMemcpyAsync(dst_hll, p->d_hll_acc, b_hll, hipMemcpyDeviceToHost, p->stream));
-  if (b_pair) HIP_TRY(hipMemcpyAsync(dst_pair, p->d_pair_acc, b_pair, hipMemcpyDeviceToHost, p->stream));
-  if (b_pred) HIP_TRY(hipMemcpyAsync(dst_pred, p->d_pred_acc, b_pred, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (b_col) DQ_HIP(hipMemcpyAsync(dst_col, p->d_col_acc, b_col, hipMemcpyDeviceToHost, p->stream));
+  if (b_hll) DQ_HIP(hipMemcpyAsync(dst_hll, p->d_hll_acc, b_hll, hipMemcpyDeviceToHost, p->stream));
+  if (b_pair) DQ_HIP(hipMemcpyAsync(dst_pair, p->d_pair_acc, b_pair, hipMemcpyDeviceToHost, p->stream));
+  if (b_pred) DQ_HIP(hipMemcpyAsync(dst_pred, p->d_pred_acc, b_pred, hipMemcpyDeviceToHost, p->stream));
+  DQ_HIP(hipStreamSynchronize(p->stream));
   if (hs) {
     if (b_col) std::memcpy(col.data(), hs, b_col);
     if (b_hll) std::memcpy(hll.data(), hs + o_hll, b_hll);
@@ -2223,7 +2215,7 @@ dq_status dq_finish(dq_plan* p, dq_state* out) {
 
 dq_status dq_plan_reset(dq_plan* p) {
   if (!p) return set_error(DQ_E_INVALID, "dq_plan_reset: plan is NULL");
-  HIP_TRY(hipSetDevice(p->device));
+  DQ_HIP(hipSetDevice(p->device));
   if (!p->parts.empty()) {
     for (dq_plan* q : p->parts)
       if (dq_status s = dq_plan_reset(q)) return s;
@@ -2249,7 +2241,7 @@ int64_t dq_plan_bytes_per_row_x1000(const dq_plan* p) { return p ? p->bytes_per_
 
 dq_status dq_plan_enable_timing(dq_plan* p, int32_t on) {
   if (!p) return set_error(DQ_E_INVALID, "dq_plan_enable_timing: plan is NULL");
-  HIP_TRY(hipSetDevice(p->device));
+  DQ_HIP(hipSetDevice(p->device));
   for (dq_plan* q : p->parts)
     if (dq_status s = dq_plan_enable_timing(q, on)) return s;
   if (dq_status s = resolve_timing(p)) return s;
@@ -2261,7 +2253,7 @@ dq_status dq_plan_enable_timing(dq_plan* p, int32_t on) {
 dq_status dq_plan_kernel_time(dq_plan* p, int32_t kernel, double* total_ms, int64_t* launches) {
   if (!p || kernel < 0 || kernel >= dq_plan::kTimers || !total_ms || !launches)
     return set_error(DQ_E_INVALID, "dq_plan_kernel_time: bad argument");
-  HIP_TRY(hipSetDevice(p->device));
+  DQ_HIP(hipSetDevice(p->device));
   if (!p->parts.empty()) {  // summed over the parts
     double ms = 0.0;
     int64_t n = 0;
@@ -2396,7 +2388,7 @@ int32_t dq_plan_pred_wait(dq_plan* p, int32_t timeout_ms) {
     return any_pred && all;
   }
   if (p->pred_jit_ref) {
-    HIP_TRY(hipSetDevice(p->device));
+    DQ_HIP(hipSetDevice(p->device));
     std::string note;
     if (hipFunction_t fn = pred_jit_poll(p->pred_jit_ref, timeout_ms, note)) {
       p->pred_jit = fn;

@@ -30,7 +30,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "dq_internal.h"
+#include "dq_hip_host.h"
 #include "dq_prim.h"
 
 namespace dq {
@@ -298,21 +298,6 @@ void launch_hist(bool append, int grid, size_t lds, hipStream_t st, const void* 
                        shift, dmask, nq, sel, hist, andor);
 }
 
-#define QHIP(x)                                                                             \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess) return set_error(DQ_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
-struct DevHist {
-  unsigned long long* p = nullptr;
-  DevHist() = default;
-  DevHist(const DevHist&) = delete;
-  ~DevHist() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // stream-ordered scratch from a pool of this library's own per device (hipMallocFromPoolAsync): the digest's
 // temporaries cost no hipMalloc / hipFree round trips across calls, while blocks beyond kPoolKeep bytes go
 // back to the device at the next synchronisation -- and torch's (the device default) pool is left alone
@@ -343,22 +328,6 @@ hipError_t scratch_pool(int device, hipMemPool_t* out) {
   *out = pool;
   return hipSuccess;
 }
-
-struct StreamTmp {
-  void* p = nullptr;
-  hipStream_t s = nullptr;
-  StreamTmp() = default;
-  StreamTmp(const StreamTmp&) = delete;
-  ~StreamTmp() {
-    if (p) (void)hipFreeAsync(p, s);
-  }
-  hipError_t alloc(size_t bytes, hipMemPool_t pool, hipStream_t st) {
-    if (p) (void)hipFreeAsync(p, s);
-    p = nullptr;
-    s = st;
-    return hipMallocFromPoolAsync(&p, std::max<size_t>(bytes, 16), pool, st);
-  }
-};
 
 double key_to_double(int32_t type, uint64_t key) {
   if (type == DQ_TYPE_F64) {
@@ -679,11 +648,10 @@ __global__ void widen_column(const void* __restrict__ src, int32_t type, void* _
 struct Widened {
   int32_t type = 0;
   std::vector<dq_column_view> views;
-  std::vector<void*> bufs;
+  std::vector<DevPtr<void>> bufs;  // (freed after the destructor has waited for the stream)
   hipStream_t stream = nullptr;
   ~Widened() {
     if (!bufs.empty()) (void)hipStreamSynchronize(stream);
-    for (void* b : bufs) (void)hipFree(b);
   }
 };
 
@@ -693,7 +661,7 @@ bool is_narrow(int32_t type) {
 
 dq_status widen(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows, int32_t n_chunks, int32_t device,
                 hipStream_t stream, Widened& w) {
-  QHIP(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   const bool to_f64 = type == DQ_TYPE_F32 || is_decimal(type);
   w.type = to_f64 ? DQ_TYPE_F64 : DQ_TYPE_I32;
   w.stream = stream;
@@ -702,12 +670,12 @@ dq_status widen(int32_t type, const dq_column_view* cols, const int64_t* chunk_r
   for (int c = 0; c < n_chunks; ++c) {
     const int64_t n = chunk_rows[c];
     if (n == 0) continue;
-    void* d = nullptr;
-    QHIP(hipMalloc(&d, (size_t)(n * bytes + 16)));
-    w.bufs.push_back(d);
+    w.bufs.emplace_back();
+    DQ_HIP(w.bufs.back().alloc((size_t)(n * bytes + 16)));
+    void* const d = w.bufs.back().get();
     const int grid = (int)std::min<int64_t>(4096, (n + 255) / 256);
     hipLaunchKernelGGL(widen_column, dim3(grid), dim3(256), 0, stream, cols[c].values, type, d, n);
-    QHIP(hipGetLastError());
+    DQ_HIP(hipGetLastError());
     w.views[c].values = d;
   }
   return DQ_OK;
@@ -754,11 +722,11 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
       return set_error(DQ_E_INVALID, "dq_approx_quantiles: chunk %d has no values", c);
     if (cols[c].reserved != 0) return set_error(DQ_E_INVALID, "dq_approx_quantiles: reserved field must be 0");
   }
-  QHIP(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
   const size_t hist_bytes = (size_t)n_q * kQBins * sizeof(unsigned long long);
-  DevHist dh;
-  QHIP(hipMalloc(&dh.p, hist_bytes));
+  DevPtr<unsigned long long> dh;
+  DQ_HIP(dh.alloc((size_t)n_q * kQBins));
   std::vector<unsigned long long> h((size_t)n_q * kQBins);
   QSelect sel{};
   std::vector<int64_t> rank(n_q, 0);  // 1-based rank still to find inside the selected prefix
@@ -766,21 +734,21 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
   // candidate lists: once every quantile's remaining candidates (the rows matching its selected
   // prefix) fit in n / 16 keys in total, the next column pass appends them, and the passes after it
   // read only those keys instead of the column
-  DevHist cand, cand_cnt;
+  DevPtr<unsigned long long> cand, cand_cnt;
   bool compacted = false;
   std::vector<int64_t> remaining(n_q, 0), cand_off(n_q, 0), cand_len(n_q, 0);
   std::vector<int> hrow(n_q);  // histogram row of quantile q in this pass
   // pass 0 also leaves the AND / OR of the non-null keys: a later pass whose digit bits are equal in every key
   // (a small-range integer column's high digits) is skipped -- its digit is known and no rank moves
-  DevHist andor_buf;
-  QHIP(hipMalloc(&andor_buf.p, 16 * kQAndOrCopies));
-  unsigned long long* const d_andor = andor_buf.p;
+  DevPtr<unsigned long long> andor_buf;
+  DQ_HIP(andor_buf.alloc(2 * kQAndOrCopies));
+  unsigned long long* const d_andor = andor_buf.get();
   unsigned long long andor0[2 * kQAndOrCopies];
   for (int i = 0; i < kQAndOrCopies; ++i) {
     andor0[2 * i] = ~0ull;
     andor0[2 * i + 1] = 0ull;
   }
-  QHIP(hipMemcpyAsync(d_andor, andor0, sizeof(andor0), hipMemcpyHostToDevice, stream));
+  DQ_HIP(hipMemcpyAsync(d_andor, andor0, sizeof(andor0), hipMemcpyHostToDevice, stream));
   uint64_t same_bits = 0;  // bits equal in every non-null key (known after pass 0)
   uint64_t or_bits = 0;
   for (int pass = 0; pass < kQPasses; ++pass) {
@@ -794,16 +762,16 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
         continue;
       }
     }
-    QHIP(hipMemsetAsync(dh.p, 0, hist_bytes, stream));
+    DQ_HIP(hipMemsetAsync(dh.get(), 0, hist_bytes, stream));
     for (int q = 0; q < n_q; ++q) hrow[q] = q;
     const uint32_t dmask32 = (1u << kQWidth[pass]) - 1u;
     if (compacted) {
       for (int q = 0; q < n_q; ++q) {
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (cand_len[q] + kQBlock * 8 - 1) / (kQBlock * 8)));
-        hipLaunchKernelGGL(dq_quantile_cand_hist, dim3(grid), dim3(kQBlock), 0, stream, cand.p + cand_off[q],
+        hipLaunchKernelGGL(dq_quantile_cand_hist, dim3(grid), dim3(kQBlock), 0, stream, cand.get() + cand_off[q],
                            (int64_t)cand_len[q], kQShift[pass], dmask32, sel.prefix[q], sel.pmask[q],
-                           dh.p + (size_t)q * kQBins);
-        QHIP(hipGetLastError());
+                           dh.get() + (size_t)q * kQBins);
+        DQ_HIP(hipGetLastError());
       }
     } else {
       // quantiles that share a selected prefix (all of them in pass 0) share one histogram row and one
@@ -827,21 +795,21 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
         int64_t total = 0;
         for (int u = 0; u < nu; ++u) total += uremaining[u];
         if (total <= std::max<int64_t>(n / 16, 1 << 16)) {
-          QHIP(hipMalloc(&cand.p, (size_t)std::max<int64_t>(total, 1) * 8));
-          QHIP(hipMalloc(&cand_cnt.p, DQ_MAX_QUANTILES * 8));
-          QHIP(hipMemsetAsync(cand_cnt.p, 0, DQ_MAX_QUANTILES * 8, stream));
+          DQ_HIP(cand.alloc((size_t)std::max<int64_t>(total, 1)));
+          DQ_HIP(cand_cnt.alloc(DQ_MAX_QUANTILES));
+          DQ_HIP(hipMemsetAsync(cand_cnt.get(), 0, DQ_MAX_QUANTILES * 8, stream));
           std::vector<int64_t> uoff(nu, 0);
           int64_t off = 0;
           for (int u = 0; u < nu; ++u) {
             uoff[u] = off;
-            usel.cand[u] = cand.p + off;
+            usel.cand[u] = cand.get() + off;
             off += uremaining[u];
           }
           for (int q = 0; q < n_q; ++q) {
             cand_off[q] = uoff[hrow[q]];
             cand_len[q] = uremaining[hrow[q]];
           }
-          usel.cand_cnt = cand_cnt.p;
+          usel.cand_cnt = cand_cnt.get();
           append = true;
         }
       }
@@ -859,21 +827,21 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
         const int sh = kQShift[pass];
         unsigned long long* const ao_p = pass == 0 ? d_andor : nullptr;
         if (type == DQ_TYPE_F64) {
-          if (aligned) launch_hist<DQ_TYPE_F64, 2>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.p, ao_p);
-          else launch_hist<DQ_TYPE_F64, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.p, ao_p);
+          if (aligned) launch_hist<DQ_TYPE_F64, 2>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          else launch_hist<DQ_TYPE_F64, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
         } else if (type == DQ_TYPE_I64) {
-          if (aligned) launch_hist<DQ_TYPE_I64, 2>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.p, ao_p);
-          else launch_hist<DQ_TYPE_I64, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.p, ao_p);
+          if (aligned) launch_hist<DQ_TYPE_I64, 2>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          else launch_hist<DQ_TYPE_I64, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
         } else {
-          if (aligned) launch_hist<DQ_TYPE_I32, 4>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.p, ao_p);
-          else launch_hist<DQ_TYPE_I32, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.p, ao_p);
+          if (aligned) launch_hist<DQ_TYPE_I32, 4>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          else launch_hist<DQ_TYPE_I32, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
         }
-        QHIP(hipGetLastError());
+        DQ_HIP(hipGetLastError());
       }
       if (append) {
         std::vector<unsigned long long> got(DQ_MAX_QUANTILES);
-        QHIP(hipMemcpyAsync(got.data(), cand_cnt.p, DQ_MAX_QUANTILES * 8, hipMemcpyDeviceToHost, stream));
-        QHIP(hipStreamSynchronize(stream));
+        DQ_HIP(hipMemcpyAsync(got.data(), cand_cnt.get(), DQ_MAX_QUANTILES * 8, hipMemcpyDeviceToHost, stream));
+        DQ_HIP(hipStreamSynchronize(stream));
         for (int u = 0; u < nu; ++u)
           if ((int64_t)got[u] != uremaining[u])
             return set_error(DQ_E_HIP, "dq_approx_quantiles: %llu candidates for prefix %d, expected %lld (data changed?)",
@@ -881,12 +849,12 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
         compacted = true;
       }
     }
-    QHIP(hipMemcpyAsync(h.data(), dh.p, hist_bytes, hipMemcpyDeviceToHost, stream));
-    QHIP(hipStreamSynchronize(stream));
+    DQ_HIP(hipMemcpyAsync(h.data(), dh.get(), hist_bytes, hipMemcpyDeviceToHost, stream));
+    DQ_HIP(hipStreamSynchronize(stream));
     if (pass == 0) {
       unsigned long long ao[2 * kQAndOrCopies];
-      QHIP(hipMemcpyAsync(ao, d_andor, sizeof(ao), hipMemcpyDeviceToHost, stream));
-      QHIP(hipStreamSynchronize(stream));
+      DQ_HIP(hipMemcpyAsync(ao, d_andor, sizeof(ao), hipMemcpyDeviceToHost, stream));
+      DQ_HIP(hipStreamSynchronize(stream));
       uint64_t k_and = ~0ull;
       or_bits = 0;
       for (int i = 0; i < kQAndOrCopies; ++i) {
@@ -958,7 +926,7 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
   }
   *n_samples = 0;
   *count = 0;
-  QHIP(hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
   if (total == 0) return DQ_OK;
   auto for_chunks = [&](auto&& launch) -> dq_status {
@@ -970,7 +938,7 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
       if (type == DQ_TYPE_F64) go(std::integral_constant<int, DQ_TYPE_F64>{});
       else if (type == DQ_TYPE_I64) go(std::integral_constant<int, DQ_TYPE_I64>{});
       else go(std::integral_constant<int, DQ_TYPE_I32>{});
-      QHIP(hipGetLastError());
+      DQ_HIP(hipGetLastError());
     }
     return DQ_OK;
   };
@@ -984,16 +952,16 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
   // one scratch block: sample keys | splitters | counts (per bucket, then keys equal to the bucket's lower
   // splitter) | cursor | sample flags | bucket flags | sorted sample keys | the sample sort's temp
   hipMemPool_t pool = nullptr;
-  QHIP(scratch_pool(device, &pool));
-  StreamTmp small;
+  DQ_HIP(scratch_pool(device, &pool));
+  StreamBuf small;
   const size_t o_spl = (size_t)ns_all * 8, o_cnt = o_spl + (size_t)(kDBuckets - 1) * 8,
                o_cur = o_cnt + (size_t)2 * kDCountCopies * kDBuckets * 8,
                o_first = o_cur + 8 + (size_t)kDAndOrCopies * 16,
                o_ok = o_first + ((size_t)(kDCells + 1) * 2 + 7) / 8 * 8, o_tgt = o_ok + (size_t)ns_all,
                o_ssorted = (o_tgt + kDBuckets + 255) & ~(size_t)255, o_stmp = o_ssorted + ((size_t)ns_all * 8 + 255) / 256 * 256;
   const size_t stb = prim::sort_temp_bytes(ns_all, 0);
-  QHIP(small.alloc(o_stmp + stb, pool, stream));
-  char* const sb = static_cast<char*>(small.p);
+  DQ_HIP(small.alloc(o_stmp + stb, pool, stream));
+  char* const sb = static_cast<char*>(small.get());
   uint16_t* const d_first = reinterpret_cast<uint16_t*>(sb + o_first);
   struct {
     unsigned long long* p;
@@ -1013,23 +981,23 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
     return st;
   // the sample sorted on the device (NULLs last; a host std::sort of 16384 keys took ~0.6-1 ms per digest, r6dg)
   unsigned long long* const d_ssorted = reinterpret_cast<unsigned long long*>(sb + o_ssorted);
-  QHIP(prim::sort_pairs(reinterpret_cast<const uint64_t*>(d_sample.p), reinterpret_cast<uint64_t*>(d_ssorted), nullptr,
+  DQ_HIP(prim::sort_pairs(reinterpret_cast<const uint64_t*>(d_sample.p), reinterpret_cast<uint64_t*>(d_ssorted), nullptr,
                         nullptr, 0, ns_all, 0, 64, false, sb + o_stmp, stb, stream));
   std::vector<unsigned long long> samp((size_t)ns_all);
   std::vector<unsigned char> sok((size_t)ns_all);
-  QHIP(hipMemcpyAsync(samp.data(), d_ssorted, (size_t)ns_all * 8, hipMemcpyDeviceToHost, stream));
-  QHIP(hipMemcpyAsync(sok.data(), d_ok.p, (size_t)ns_all, hipMemcpyDeviceToHost, stream));
-  QHIP(hipStreamSynchronize(stream));
+  DQ_HIP(hipMemcpyAsync(samp.data(), d_ssorted, (size_t)ns_all * 8, hipMemcpyDeviceToHost, stream));
+  DQ_HIP(hipMemcpyAsync(sok.data(), d_ok.p, (size_t)ns_all, hipMemcpyDeviceToHost, stream));
+  DQ_HIP(hipStreamSynchronize(stream));
   size_t nv = 0;
   for (unsigned char f : sok) nv += f;
   samp.resize(nv);  // the valid keys in order: every NULL's ~0 is at or past position nv
   std::vector<unsigned long long> spl(kDBuckets - 1, ~0ull);  // no sample: one bucket holds every key
   for (int k = 1; k < kDBuckets && nv > 0; ++k) spl[(size_t)k - 1] = samp[(size_t)k * nv / kDBuckets];
-  QHIP(hipMemcpyAsync(d_spl.p, spl.data(), (size_t)(kDBuckets - 1) * 8, hipMemcpyHostToDevice, stream));
+  DQ_HIP(hipMemcpyAsync(d_spl.p, spl.data(), (size_t)(kDBuckets - 1) * 8, hipMemcpyHostToDevice, stream));
   std::vector<uint16_t> first;
   const DigestCells C = digest_cells(type, spl, first);
-  QHIP(hipMemcpyAsync(d_first, first.data(), first.size() * 2, hipMemcpyHostToDevice, stream));
-  QHIP(hipMemsetAsync(d_counts.p, 0, (size_t)2 * kDCountCopies * kDBuckets * 8, stream));
+  DQ_HIP(hipMemcpyAsync(d_first, first.data(), first.size() * 2, hipMemcpyHostToDevice, stream));
+  DQ_HIP(hipMemsetAsync(d_counts.p, 0, (size_t)2 * kDCountCopies * kDBuckets * 8, stream));
   // 2. per-bucket counts (and of each bucket's keys equal to its lower splitter)
   if (dq_status st = for_chunks([&](auto tk, int grid, int c, int64_t rows) {
         hipLaunchKernelGGL((dq_digest_pass<decltype(tk)::value, true>), dim3(grid), dim3(kQBlock), 0, stream,
@@ -1039,8 +1007,8 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
     return st;
   std::vector<unsigned long long> cnt_copies((size_t)2 * kDCountCopies * kDBuckets), cnt((size_t)kDBuckets, 0),
       eq((size_t)kDBuckets, 0);
-  QHIP(hipMemcpyAsync(cnt_copies.data(), d_counts.p, cnt_copies.size() * 8, hipMemcpyDeviceToHost, stream));
-  QHIP(hipStreamSynchronize(stream));
+  DQ_HIP(hipMemcpyAsync(cnt_copies.data(), d_counts.p, cnt_copies.size() * 8, hipMemcpyDeviceToHost, stream));
+  DQ_HIP(hipStreamSynchronize(stream));
   for (size_t i = 0; i < (size_t)kDCountCopies * kDBuckets; ++i) {
     cnt[i % kDBuckets] += cnt_copies[i];
     eq[i % kDBuckets] += cnt_copies[(size_t)kDCountCopies * kDBuckets + i];
@@ -1106,11 +1074,11 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
   }
   // second scratch block: candidates | sorted candidates | sample indices | gathered keys | radix-sort temp
   const size_t tb = prim::sort_temp_bytes(std::max<int64_t>(1, batch_max), 0);
-  StreamTmp big;
+  StreamBuf big;
   const size_t o_sorted = (size_t)batch_max * 8, o_idx = o_sorted + (size_t)batch_max * 8,
                o_got = o_idx + (size_t)m * 8, o_tmp = (o_got + (size_t)m * 8 + 255) & ~(size_t)255;
-  QHIP(big.alloc(o_tmp + tb, pool, stream));
-  char* const bb = static_cast<char*>(big.p);
+  DQ_HIP(big.alloc(o_tmp + tb, pool, stream));
+  char* const bb = static_cast<char*>(big.get());
   unsigned long long* const cand = reinterpret_cast<unsigned long long*>(bb);
   unsigned long long* const sorted = reinterpret_cast<unsigned long long*>(bb + o_sorted);
   long long* const d_idx = reinterpret_cast<long long*>(bb + o_idx);
@@ -1130,9 +1098,9 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
         nc += (int64_t)(cnt[(size_t)b] - eq[(size_t)b]);
       }
     }
-    QHIP(hipMemcpyAsync(d_target.p, tgt.data(), (size_t)kDBuckets, hipMemcpyHostToDevice, stream));
+    DQ_HIP(hipMemcpyAsync(d_target.p, tgt.data(), (size_t)kDBuckets, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(dq_digest_cursor_init, dim3(1), dim3(64), 0, stream, d_cursor.p);
-    QHIP(hipGetLastError());
+    DQ_HIP(hipGetLastError());
     if (dq_status st = for_chunks([&](auto tk, int grid, int c, int64_t rows) {
           hipLaunchKernelGGL((dq_digest_pass<decltype(tk)::value, false>), dim3(grid), dim3(kQBlock), 0, stream,
                              cols[c].values, reinterpret_cast<const uint32_t*>(cols[c].validity), rows, d_spl.p,
@@ -1141,8 +1109,8 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
       return st;
     // the candidates agree above their highest differing bit: sorting the bits below gives the full order
     unsigned long long cur[1 + 2 * kDAndOrCopies];
-    QHIP(hipMemcpyAsync(cur, d_cursor.p, sizeof(cur), hipMemcpyDeviceToHost, stream));
-    QHIP(hipStreamSynchronize(stream));
+    DQ_HIP(hipMemcpyAsync(cur, d_cursor.p, sizeof(cur), hipMemcpyDeviceToHost, stream));
+    DQ_HIP(hipStreamSynchronize(stream));
     if ((int64_t)cur[0] != nc)
       return set_error(DQ_E_HIP, "dq_quantile_digest: %llu candidates, the count pass expected %lld (data changed?)",
                        cur[0], (long long)nc);
@@ -1153,7 +1121,7 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
     }
     const int end_bit = (c_and ^ c_or) ? 64 - __builtin_clzll(c_and ^ c_or) : 1;
     if (nc > 0)
-      QHIP(prim::sort_pairs(reinterpret_cast<const uint64_t*>(cand), reinterpret_cast<uint64_t*>(sorted), nullptr, nullptr,
+      DQ_HIP(prim::sort_pairs(reinterpret_cast<const uint64_t*>(cand), reinterpret_cast<uint64_t*>(sorted), nullptr, nullptr,
                             0, nc, 0, end_bit, false, bb + o_tmp, tb, stream));
     // 4. sample i = the sorted candidate at (its rank within its bucket, past the bucket's eq keys) + (the batch's
     // candidates of the buckets before)
@@ -1166,12 +1134,12 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
     }
     const int64_t mb = (int64_t)idx.size();
     if (mb > 0) {
-      QHIP(hipMemcpyAsync(d_idx, idx.data(), (size_t)mb * 8, hipMemcpyHostToDevice, stream));
+      DQ_HIP(hipMemcpyAsync(d_idx, idx.data(), (size_t)mb * 8, hipMemcpyHostToDevice, stream));
       hipLaunchKernelGGL(dq_digest_gather, dim3((unsigned)((mb + 255) / 256)), dim3(256), 0, stream, sorted, d_idx, mb,
                          d_got);
-      QHIP(hipGetLastError());
-      QHIP(hipMemcpyAsync(got.data() + s0, d_got, (size_t)mb * 8, hipMemcpyDeviceToHost, stream));
-      QHIP(hipStreamSynchronize(stream));
+      DQ_HIP(hipGetLastError());
+      DQ_HIP(hipMemcpyAsync(got.data() + s0, d_got, (size_t)mb * 8, hipMemcpyDeviceToHost, stream));
+      DQ_HIP(hipStreamSynchronize(stream));
     }
   }
   for (int64_t i = 0; i < m; ++i) {

@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "dq_internal.h"
+#include "dq_hip_host.h"
 #include "dq_prim.h"
 #include "dq_regex.h"
 #include "dq_schema.h"
@@ -237,21 +237,6 @@ __global__ void dq_take_strings(const uint32_t* __restrict__ src_words, const Of
   for (; i < n; ++i) out_bytes[d + i] = src[s + i];
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-#define CHIP(what, call)                                                                             \
-  do {                                                                                               \
-    const hipError_t e_ = (call);                                                                    \
-    if (e_ != hipSuccess)                                                                            \
-      return set_error(e_ == hipErrorOutOfMemory ? DQ_E_OOM : DQ_E_HIP, "%s: %s failed: %s", what, #call, \
-                       hipGetErrorString(e_));                                                       \
-  } while (0)
-
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 int fixed_width(int32_t type) {
@@ -277,16 +262,13 @@ struct dq_schema_plan {
   std::vector<uint16_t> regex;             // regex_serialize blobs, back to back
   std::vector<dq::SchemaColDev> cols;      // staging of one call's pointers
   int32_t device = -1;                     // where the device copies live (-1: nowhere yet)
-  void* d_defs = nullptr;
-  void* d_masks = nullptr;
-  void* d_regex = nullptr;
-  void* d_cols = nullptr;
-  void* d_counters = nullptr;
+  dq::DevPtr<dq::SchemaDef> d_defs;
+  dq::DevPtr<dq::SchemaMaskEl> d_masks;
+  dq::DevPtr<uint16_t> d_regex;
+  dq::DevPtr<dq::SchemaColDev> d_cols;
+  dq::DevPtr<unsigned long long> d_counters;
   void release() {
-    for (void** p : {&d_defs, &d_masks, &d_regex, &d_cols, &d_counters}) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
+    d_defs.reset(), d_masks.reset(), d_regex.reset(), d_cols.reset(), d_counters.reset();
     device = -1;
   }
 };
@@ -398,33 +380,32 @@ dq_status dq_schema_validate(dq_schema_plan* plan, const int32_t* types, const d
     }
   }
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  CHIP(me, hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   if (plan->device != device) {  // the plan's constants move to the device it is first used on
     plan->release();
     const size_t nd = plan->defs.size() ? plan->defs.size() : 1;
-    CHIP(me, hipMalloc(&plan->d_defs, nd * sizeof(SchemaDef)));
-    CHIP(me, hipMalloc(&plan->d_cols, nd * sizeof(SchemaColDev)));
-    CHIP(me, hipMalloc(&plan->d_masks, (plan->masks.size() + 1) * sizeof(SchemaMaskEl)));
-    CHIP(me, hipMalloc(&plan->d_regex, (plan->regex.size() + 2) * sizeof(uint16_t)));
-    CHIP(me, hipMalloc(&plan->d_counters, 16));
+    DQ_HIP(plan->d_defs.alloc(nd));
+    DQ_HIP(plan->d_cols.alloc(nd));
+    DQ_HIP(plan->d_masks.alloc(plan->masks.size() + 1));
+    DQ_HIP(plan->d_regex.alloc(plan->regex.size() + 2));
+    DQ_HIP(plan->d_counters.alloc(2));
     plan->device = device;
-    if (!plan->defs.empty()) CHIP(me, hipMemcpy(plan->d_defs, plan->defs.data(), plan->defs.size() * sizeof(SchemaDef), hipMemcpyHostToDevice));
-    if (!plan->masks.empty()) CHIP(me, hipMemcpy(plan->d_masks, plan->masks.data(), plan->masks.size() * sizeof(SchemaMaskEl), hipMemcpyHostToDevice));
-    if (!plan->regex.empty()) CHIP(me, hipMemcpy(plan->d_regex, plan->regex.data(), plan->regex.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if (!plan->defs.empty()) DQ_HIP(hipMemcpy(plan->d_defs.get(), plan->defs.data(), plan->defs.size() * sizeof(SchemaDef), hipMemcpyHostToDevice));
+    if (!plan->masks.empty()) DQ_HIP(hipMemcpy(plan->d_masks.get(), plan->masks.data(), plan->masks.size() * sizeof(SchemaMaskEl), hipMemcpyHostToDevice));
+    if (!plan->regex.empty()) DQ_HIP(hipMemcpy(plan->d_regex.get(), plan->regex.data(), plan->regex.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
   }
-  if (n_defs > 0) CHIP(me, hipMemcpyAsync(plan->d_cols, plan->cols.data(), (size_t)n_defs * sizeof(SchemaColDev), hipMemcpyHostToDevice, st));
-  CHIP(me, hipMemsetAsync(plan->d_counters, 0, 16, st));
+  if (n_defs > 0) DQ_HIP(hipMemcpyAsync(plan->d_cols.get(), plan->cols.data(), (size_t)n_defs * sizeof(SchemaColDev), hipMemcpyHostToDevice, st));
+  DQ_HIP(hipMemsetAsync(plan->d_counters.get(), 0, 16, st));
   const int regex_words = (int)plan->regex.size();
   const int lds_words = regex_words <= kDfaLdsWords ? regex_words : 0;
   hipLaunchKernelGGL(dq_schema_verdict_kernel, dim3(grid_for(n_rows, kRowsPerBlock)), dim3(kSchemaBlock),
-                     (size_t)lds_words * sizeof(uint16_t), st, static_cast<const SchemaDef*>(plan->d_defs),
-                     static_cast<const SchemaColDev*>(plan->d_cols), n_defs, static_cast<const SchemaMaskEl*>(plan->d_masks),
-                     static_cast<const uint16_t*>(plan->d_regex), lds_words, n_rows, valid_bitmap, invalid_bitmap,
-                     static_cast<unsigned long long*>(plan->d_counters));
-  CHIP(me, hipGetLastError());
+                     (size_t)lds_words * sizeof(uint16_t), st, plan->d_defs.get(), plan->d_cols.get(), n_defs,
+                     plan->d_masks.get(), plan->d_regex.get(), lds_words, n_rows, valid_bitmap, invalid_bitmap,
+                     plan->d_counters.get());
+  DQ_HIP(hipGetLastError());
   unsigned long long h[2] = {0, 0};
-  CHIP(me, hipMemcpyAsync(h, plan->d_counters, 16, hipMemcpyDeviceToHost, st));
-  CHIP(me, hipStreamSynchronize(st));
+  DQ_HIP(hipMemcpyAsync(h, plan->d_counters.get(), 16, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
   if (num_valid) *num_valid = (int64_t)h[0];
   if (num_invalid) *num_invalid = (int64_t)h[1];
   return DQ_OK;
@@ -471,26 +452,27 @@ dq_status dq_take_index(const uint64_t* selection, int64_t n_rows, int64_t n_sel
   if (!selection || ((uintptr_t)selection & 7) || (n_selected > 0 && (!index || ((uintptr_t)index & 7))))
     return set_error(DQ_E_INVALID, "%s: NULL or misaligned buffer", me);
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  CHIP(me, hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   const int64_t nw = (n_rows + 63) >> 6;
-  DevBuf counts, temp;
-  CHIP(me, hipMalloc(&counts.p, (size_t)(nw + 1) * 8));
-  CHIP(me, hipMalloc(&temp.p, prim::scan_temp_bytes(nw + 1) + 16));
-  auto* dc = static_cast<int64_t*>(counts.p);
-  CHIP(me, hipMemsetAsync(dc + nw, 0, 8, st));
+  DevPtr<int64_t> counts;
+  DevPtr<void> temp;
+  DQ_HIP(counts.alloc((size_t)(nw + 1)));
+  DQ_HIP(temp.alloc(prim::scan_temp_bytes(nw + 1) + 16));
+  int64_t* const dc = counts.get();
+  DQ_HIP(hipMemsetAsync(dc + nw, 0, 8, st));
   hipLaunchKernelGGL(dq_take_popcount, dim3(grid_for(nw, kTakeBlock)), dim3(kTakeBlock), 0, st, selection, n_rows, nw, dc);
-  CHIP(me, hipGetLastError());
-  CHIP(me, prim::exclusive_sum_i64(dc, dc, nw + 1, temp.p, st));  // dc[nw] = the number of selected rows
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(prim::exclusive_sum_i64(dc, dc, nw + 1, temp.get(), st));  // dc[nw] = the number of selected rows
   int64_t total = -1;
-  CHIP(me, hipMemcpyAsync(&total, dc + nw, 8, hipMemcpyDeviceToHost, st));
-  CHIP(me, hipStreamSynchronize(st));
+  DQ_HIP(hipMemcpyAsync(&total, dc + nw, 8, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
   if (total != n_selected)
     return set_error(DQ_E_INVALID, "%s: the bitmap selects %lld rows, not %lld", me, (long long)total, (long long)n_selected);
   if (n_selected == 0) return DQ_OK;
   hipLaunchKernelGGL(dq_take_scatter_index, dim3(grid_for(n_rows, kTakeBlock)), dim3(kTakeBlock), 0, st, selection, dc,
                      n_rows, n_selected, index);
-  CHIP(me, hipGetLastError());
-  CHIP(me, hipStreamSynchronize(st));  // (the scratch is freed on return)
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(hipStreamSynchronize(st));  // (the scratch is freed on return)
   return DQ_OK;
 }
 
@@ -511,13 +493,13 @@ dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, 
       ((uintptr_t)src->validity & 3) || ((uintptr_t)out_offsets & 7) || ((uintptr_t)src->offsets & 3) || ((uintptr_t)index & 7))
     return set_error(DQ_E_INVALID, "%s: misaligned buffer", me);
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  CHIP(me, hipSetDevice(device));
+  DQ_HIP(hipSetDevice(device));
   const unsigned grid = grid_for(n_selected, kTakeBlock), grid1 = grid_for(n_selected + 1, kTakeBlock);
   const unsigned grid_bits = grid_for(((n_selected + 63) >> 6) * 64, kTakeBlock);
   if (out_validity) {
     hipLaunchKernelGGL(dq_take_bits, dim3(grid_bits), dim3(kTakeBlock), 0, st, reinterpret_cast<const uint32_t*>(src->validity),
                        index, n_selected, n_rows, reinterpret_cast<uint64_t*>(out_validity));
-    CHIP(me, hipGetLastError());
+    DQ_HIP(hipGetLastError());
   }
   if (!str) {
     const int w = fixed_width(type);
@@ -537,22 +519,23 @@ dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, 
                            index, n_selected, n_rows, static_cast<uint64_t*>(out_values));
     }
 #undef DQ_TAKE_FIXED
-    CHIP(me, hipGetLastError());
-    CHIP(me, hipStreamSynchronize(st));
+    DQ_HIP(hipGetLastError());
+    DQ_HIP(hipStreamSynchronize(st));
     return DQ_OK;
   }
   if (!large && n_selected >= INT32_MAX) return set_error(DQ_E_INVALID, "%s: UTF8 chunk of %lld rows", me, (long long)n_selected);
-  DevBuf lens, temp;
-  CHIP(me, hipMalloc(&lens.p, (size_t)(n_selected + 1) * 8));
-  CHIP(me, hipMalloc(&temp.p, prim::scan_temp_bytes(n_selected + 1) + 16));
-  auto* dl = static_cast<int64_t*>(lens.p);
+  DevPtr<int64_t> lens;
+  DevPtr<void> temp;
+  DQ_HIP(lens.alloc((size_t)(n_selected + 1)));
+  DQ_HIP(temp.alloc(prim::scan_temp_bytes(n_selected + 1) + 16));
+  int64_t* const dl = lens.get();
   if (large) hipLaunchKernelGGL(dq_take_lengths<int64_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const int64_t*>(src->offsets), index, n_selected, n_rows, dl);
   else hipLaunchKernelGGL(dq_take_lengths<int32_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const int32_t*>(src->offsets), index, n_selected, n_rows, dl);
-  CHIP(me, hipGetLastError());
-  CHIP(me, prim::exclusive_sum_i64(dl, dl, n_selected + 1, temp.p, st));
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(prim::exclusive_sum_i64(dl, dl, n_selected + 1, temp.get(), st));
   int64_t total = 0;
-  CHIP(me, hipMemcpyAsync(&total, dl + n_selected, 8, hipMemcpyDeviceToHost, st));
-  CHIP(me, hipStreamSynchronize(st));
+  DQ_HIP(hipMemcpyAsync(&total, dl + n_selected, 8, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
   if (data_bytes) *data_bytes = total;
   if (!large && total > INT32_MAX) return set_error(DQ_E_INVALID, "%s: %lld bytes do not fit UTF8 offsets", me, (long long)total);
   if (out_values && values_capacity < total)
@@ -560,8 +543,8 @@ dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, 
   // (out_values NULL: the sizing call -- offsets and *data_bytes only)
   if (large) hipLaunchKernelGGL(dq_take_strings<int64_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const uint32_t*>(src->values), static_cast<const int64_t*>(src->offsets), index, dl, n_selected, n_rows, static_cast<int64_t*>(out_offsets), static_cast<uint8_t*>(out_values));
   else hipLaunchKernelGGL(dq_take_strings<int32_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const uint32_t*>(src->values), static_cast<const int32_t*>(src->offsets), index, dl, n_selected, n_rows, static_cast<int32_t*>(out_offsets), static_cast<uint8_t*>(out_values));
-  CHIP(me, hipGetLastError());
-  CHIP(me, hipStreamSynchronize(st));
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(hipStreamSynchronize(st));
   return DQ_OK;
 }
 

@@ -17,7 +17,7 @@
 #include <cmath>
 
 #include "dq_hash.h"
-#include "dq_internal.h"
+#include "dq_hip_host.h"
 
 namespace dq {
 namespace {
@@ -69,21 +69,6 @@ __global__ __launch_bounds__(kSplitBlock) void dq_split_kernel(int64_t n_rows, u
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-#define CHIP(what, call)                                                                             \
-  do {                                                                                               \
-    const hipError_t e_ = (call);                                                                    \
-    if (e_ != hipSuccess)                                                                            \
-      return set_error(e_ == hipErrorOutOfMemory ? DQ_E_OOM : DQ_E_HIP, "%s: %s failed: %s", what, #call, \
-                       hipGetErrorString(e_));                                                       \
-  } while (0)
-
 // the argument checks both entry points share; rows are numbered row0 .. row0 + n_rows - 1 in int64
 dq_status split_check(const char* me, int64_t n_rows, int64_t row0, double test_ratio) {
   if (n_rows < 0 || row0 < 0 || row0 > INT64_MAX - n_rows) return set_error(DQ_E_INVALID, "%s: bad row range", me);
@@ -109,19 +94,19 @@ dq_status dq_split_rows(int64_t n_rows, int64_t row0, uint64_t seed, double test
   if (!train_bitmap || !test_bitmap || ((uintptr_t)train_bitmap & 7) || ((uintptr_t)test_bitmap & 7))
     return set_error(DQ_E_INVALID, "%s: NULL or misaligned bitmap", me);
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  CHIP(me, hipSetDevice(device));
-  DevBuf counter;
-  CHIP(me, hipMalloc(&counter.p, 8));
-  CHIP(me, hipMemsetAsync(counter.p, 0, 8, st));
+  DQ_HIP(hipSetDevice(device));
+  DevPtr<unsigned long long> counter;
+  DQ_HIP(counter.alloc(1));
+  DQ_HIP(hipMemsetAsync(counter.get(), 0, 8, st));
   const int64_t n_words = (n_rows + 63) >> 6;
   const int64_t blocks = (n_words + kSplitWaves - 1) / kSplitWaves;
   const unsigned grid = (unsigned)(blocks < kSplitMaxGrid ? blocks : kSplitMaxGrid);
   hipLaunchKernelGGL(dq_split_kernel, dim3(grid), dim3(kSplitBlock), 0, st, n_rows, (uint64_t)row0, seed, test_ratio,
-                     train_bitmap, test_bitmap, static_cast<unsigned long long*>(counter.p));
-  CHIP(me, hipGetLastError());
+                     train_bitmap, test_bitmap, counter.get());
+  DQ_HIP(hipGetLastError());
   unsigned long long h = 0;
-  CHIP(me, hipMemcpyAsync(&h, counter.p, 8, hipMemcpyDeviceToHost, st));
-  CHIP(me, hipStreamSynchronize(st));
+  DQ_HIP(hipMemcpyAsync(&h, counter.get(), 8, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
   if (num_test) *num_test = (int64_t)h;
   if (num_train) *num_train = n_rows - (int64_t)h;
   return DQ_OK;
