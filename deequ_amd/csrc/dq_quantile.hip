@@ -23,10 +23,12 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -681,6 +683,54 @@ dq_status widen(int32_t type, const dq_column_view* cols, const int64_t* chunk_r
   return DQ_OK;
 }
 
+// java.lang.Double.toString of v, as the reference's parameter messages print it: NaN, Infinity, plain decimal for
+// 1e-3 <= |v| < 1e7 and d.dddE<n> otherwise, on the shortest digits that read back as v
+std::string java_double_string(double v) {
+  if (v != v) return "NaN";
+  if (v - v != 0.0) return v < 0.0 ? "-Infinity" : "Infinity";
+  const std::string sign = std::signbit(v) ? "-" : "";
+  if (v == 0.0) return sign + "0.0";
+  char e[40];
+  for (int p = 0; p <= 16; ++p) {
+    std::snprintf(e, sizeof(e), "%.*e", p, std::fabs(v));
+    if (std::strtod(e, nullptr) == std::fabs(v)) break;
+  }
+  std::string digits(1, e[0]);  // e = d[.ddd]e[+-]xx
+  const char* const ep = std::strchr(e, 'e');
+  if (e[1] == '.') digits.append(e + 2, (size_t)(ep - (e + 2)));
+  const int x = std::atoi(ep + 1);
+  if (x < 0 && x >= -3) return sign + "0." + std::string((size_t)(-x - 1), '0') + digits;
+  const size_t whole = x >= 7 || x < 0 ? 1 : (size_t)x + 1;  // digits ahead of the point
+  if (digits.size() < whole) digits.append(whole - digits.size(), '0');
+  const std::string frac = digits.size() > whole ? digits.substr(whole) : "0";
+  return sign + digits.substr(0, whole) + "." + frac + (whole == 1 && x != 0 ? "E" + std::to_string(x) : "");
+}
+
+// The argument checks both entry points share, ahead of any device work (a narrow column is checked before it is
+// widened): the type, ApproxQuantile.scala:46-56's PARAM_CHECKS with MetricCalculationException's messages, then
+// every chunk's row count, values pointer and reserved field.
+dq_status check_quantile_args(const char* fn, int32_t type, const dq_column_view* cols, const int64_t* chunk_rows,
+                              int32_t n_chunks, const double* quantiles, int32_t n_q, double relative_error) {
+  if (!is_narrow(type) && type != DQ_TYPE_F64 && type != DQ_TYPE_I64 && type != DQ_TYPE_I32)
+    return set_error(DQ_E_TYPE, "%s: column type %d is not numeric", fn, type);
+  for (int q = 0; q < n_q; ++q)
+    if (!(quantiles[q] >= 0.0 && quantiles[q] <= 1.0))
+      return set_error(DQ_E_INVALID,
+                       "Quantile parameter must be in the closed interval [0, 1]. Currently, the value is: %s!",
+                       java_double_string(quantiles[q]).c_str());
+  if (!(relative_error >= 0.0 && relative_error <= 1.0))
+    return set_error(DQ_E_INVALID,
+                     "Relative error parameter must be in the closed interval [0, 1]. Currently, the value is: %s!",
+                     java_double_string(relative_error).c_str());
+  for (int c = 0; c < n_chunks; ++c) {
+    if (chunk_rows[c] < 0 || chunk_rows[c] > ((int64_t)1 << 40))
+      return set_error(DQ_E_INVALID, "%s: chunk %d has %lld rows", fn, c, (long long)chunk_rows[c]);
+    if (chunk_rows[c] > 0 && !cols[c].values) return set_error(DQ_E_INVALID, "%s: chunk %d has no values", fn, c);
+    if (cols[c].reserved != 0) return set_error(DQ_E_INVALID, "%s: reserved field must be 0", fn);
+  }
+  return DQ_OK;
+}
+
 }  // namespace
 }  // namespace dq
 
@@ -695,32 +745,14 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
     return set_error(DQ_E_INVALID, "dq_approx_quantiles: NULL argument");
   if (n_q < 1 || n_q > DQ_MAX_QUANTILES)
     return set_error(DQ_E_INVALID, "dq_approx_quantiles: %d quantiles (1..%d per call)", n_q, DQ_MAX_QUANTILES);
+  if (dq_status s = check_quantile_args("dq_approx_quantiles", type, cols, chunk_rows, n_chunks, quantiles, n_q,
+                                        relative_error))
+    return s;
   if (is_narrow(type)) {
-    for (int c = 0; c < n_chunks; ++c)
-      if (chunk_rows[c] > 0 && !cols[c].values) return set_error(DQ_E_INVALID, "dq_approx_quantiles: chunk %d has no values", c);
     Widened w;
     if (dq_status s = widen(type, cols, chunk_rows, n_chunks, device, reinterpret_cast<hipStream_t>(hip_stream), w)) return s;
     return dq_approx_quantiles(w.type, w.views.data(), chunk_rows, n_chunks, quantiles, n_q, relative_error, device,
                                hip_stream, out, count);
-  }
-  if (type != DQ_TYPE_F64 && type != DQ_TYPE_I64 && type != DQ_TYPE_I32)
-    return set_error(DQ_E_TYPE, "dq_approx_quantiles: column type %d is not numeric", type);
-  // ApproxQuantile.scala:46-56 PARAM_CHECKS (MetricCalculationException messages)
-  for (int q = 0; q < n_q; ++q)
-    if (!(quantiles[q] >= 0.0 && quantiles[q] <= 1.0))
-      return set_error(DQ_E_INVALID,
-                       "Quantile parameter must be in the closed interval [0, 1]. Currently, the value is: %g!",
-                       quantiles[q]);
-  if (!(relative_error >= 0.0 && relative_error <= 1.0))
-    return set_error(DQ_E_INVALID,
-                     "Relative error parameter must be in the closed interval [0, 1]. Currently, the value is: %g!",
-                     relative_error);
-  for (int c = 0; c < n_chunks; ++c) {
-    if (chunk_rows[c] < 0 || chunk_rows[c] > ((int64_t)1 << 40))
-      return set_error(DQ_E_INVALID, "dq_approx_quantiles: chunk %d has %lld rows", c, (long long)chunk_rows[c]);
-    if (chunk_rows[c] > 0 && !cols[c].values)
-      return set_error(DQ_E_INVALID, "dq_approx_quantiles: chunk %d has no values", c);
-    if (cols[c].reserved != 0) return set_error(DQ_E_INVALID, "dq_approx_quantiles: reserved field must be 0");
   }
   DQ_HIP(hipSetDevice(device));
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
@@ -901,29 +933,17 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
                              int64_t cap, int64_t* n_samples, int64_t* count) {
   if (!cols || !chunk_rows || !n_samples || !count || n_chunks < 0 || cap < 0 || (cap > 0 && (!values || !ranks)))
     return set_error(DQ_E_INVALID, "dq_quantile_digest: NULL argument");
+  if (dq_status s = check_quantile_args("dq_quantile_digest", type, cols, chunk_rows, n_chunks, nullptr, 0,
+                                        relative_error))
+    return s;
   if (is_narrow(type)) {
-    for (int c = 0; c < n_chunks; ++c)
-      if (chunk_rows[c] > 0 && !cols[c].values) return set_error(DQ_E_INVALID, "dq_quantile_digest: chunk %d has no values", c);
     Widened w;
     if (dq_status s = widen(type, cols, chunk_rows, n_chunks, device, reinterpret_cast<hipStream_t>(hip_stream), w)) return s;
     return dq_quantile_digest(w.type, w.views.data(), chunk_rows, n_chunks, relative_error, device, hip_stream, values,
                               ranks, cap, n_samples, count);
   }
-  if (type != DQ_TYPE_F64 && type != DQ_TYPE_I64 && type != DQ_TYPE_I32)
-    return set_error(DQ_E_TYPE, "dq_quantile_digest: column type %d is not numeric", type);
-  if (!(relative_error >= 0.0 && relative_error <= 1.0))
-    return set_error(DQ_E_INVALID,
-                     "Relative error parameter must be in the closed interval [0, 1]. Currently, the value is: %g!",
-                     relative_error);
   int64_t total = 0;
-  for (int c = 0; c < n_chunks; ++c) {
-    if (chunk_rows[c] < 0 || chunk_rows[c] > ((int64_t)1 << 40))
-      return set_error(DQ_E_INVALID, "dq_quantile_digest: chunk %d has %lld rows", c, (long long)chunk_rows[c]);
-    if (chunk_rows[c] > 0 && !cols[c].values)
-      return set_error(DQ_E_INVALID, "dq_quantile_digest: chunk %d has no values", c);
-    if (cols[c].reserved != 0) return set_error(DQ_E_INVALID, "dq_quantile_digest: reserved field must be 0");
-    total += chunk_rows[c];
-  }
+  for (int c = 0; c < n_chunks; ++c) total += chunk_rows[c];
   *n_samples = 0;
   *count = 0;
   DQ_HIP(hipSetDevice(device));
