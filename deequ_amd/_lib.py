@@ -26,6 +26,9 @@ TYPE_F64, TYPE_I64, TYPE_I32, TYPE_UTF8, TYPE_LARGE_UTF8 = 1, 2, 3, 4, 5
 TYPE_F32, TYPE_I16, TYPE_I8, TYPE_BOOL, TYPE_DATE32, TYPE_TIMESTAMP = 6, 7, 8, 9, 10, 11
 # DecimalType(p, s): 16-byte two's-complement unscaled values; its type code carries p and s (DQ_DECIMAL128)
 TYPE_DECIMAL128 = 12
+# StringType as int32 indices into a dictionary of strings (view: values = indices, offsets = entry words, reserved = D)
+TYPE_DICT_UTF8 = 13
+DICT_TIMER = 4  # dq_plan_kernel_time id of the dictionary row pass (dq_device.h kDictTimer)
 
 
 def decimal_type(precision: int, scale: int) -> int:
@@ -349,6 +352,15 @@ def _load():
     L.dq_state_from_bytes.argtypes = [c.c_int32, c.c_char_p, c.c_int64, P(State)]
     L.dq_state_identifier.restype = c.c_int32
     L.dq_state_identifier.argtypes = [c.c_char_p]
+    L.dq_dict_entries.restype = c.c_int32
+    L.dq_dict_entries.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_void_p, c.c_int32, c.c_void_p]
+    L.dq_dict_decode.restype = c.c_int32
+    L.dq_dict_decode.argtypes = [c.c_int32, P(ColumnView), c.c_int64, P(ColumnView), c.c_int64, c.c_void_p, c.c_int64,
+                                 c.c_void_p, c.c_void_p, P(c.c_int64), c.c_int32, c.c_void_p]
+    L.dq_dict_check_indices.restype = c.c_int32
+    L.dq_dict_check_indices.argtypes = [c.c_int32, c.c_void_p, c.c_int64, c.c_void_p, c.c_int32, c.c_int64, c.c_void_p]
+    L.dq_arrow_import_dictionary.restype = c.c_int32
+    L.dq_arrow_import_dictionary.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     if L.dq_abi_version() != ABI_VERSION:
         raise ImportError(f"libdqscan ABI {L.dq_abi_version()} != {ABI_VERSION}")
     return L
@@ -381,6 +393,7 @@ EXPORTED = [
     "dq_cat_hist_capacity", "dq_cat_hist_build", "dq_cat_hist_column", "dq_cat_hist_export", "dq_cat_hist_destroy",
     "dq_schema_plan_create", "dq_schema_plan_destroy", "dq_schema_validate", "dq_schema_check_host",
     "dq_take_index", "dq_take_rows", "dq_split_rows", "dq_split_rows_host",
+    "dq_dict_entries", "dq_dict_decode", "dq_dict_check_indices", "dq_arrow_import_dictionary",
 ]
 
 

@@ -28,7 +28,7 @@ Schema = Sequence  # list of (name, dtype, nullable)
 # the Spark SQL type each column dtype carries (WrongColumnTypeException text, Analyzer.scala:330-332)
 SPARK_TYPE = {"f64": "DoubleType", "f32": "FloatType", "i64": "LongType", "i32": "IntegerType", "i16": "ShortType",
               "i8": "ByteType", "bool": "BooleanType", "date32": "DateType", "timestamp": "TimestampType",
-              "utf8": "StringType", "large_utf8": "StringType"}
+              "utf8": "StringType", "large_utf8": "StringType", "dict_utf8": "StringType"}
 
 
 def spark_type(dtype: str) -> str:

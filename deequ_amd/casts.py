@@ -62,6 +62,11 @@ def cast_numeric_string_columns(data: Union[Table, Sequence[Table]], inferred: D
     """castNumericStringColumns over a Table or a list of chunk Tables: every string column whose inferred type
     (DataTypeHistogram.determineType) is Integral becomes i64, Fractional f64; the others and the column order are
     kept (castColumn's withColumn / drop / rename keeps the name; the order is kept here for every column)."""
+    from .table import plain_utf8
+
+    # (a dictionary-encoded column that is cast is read as the plain column it stands for; the others stay encoded)
+    data = plain_utf8(data, [n for n, t in inferred.items() if _CAST_OF.get(t)])
+
     def one(t: Table) -> Table:
         cols = []
         for c in t.columns.values():

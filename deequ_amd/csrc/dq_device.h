@@ -288,6 +288,22 @@ struct ScanCols {
   const void* offsets[kMaxCols];
 };
 
+// Dictionary columns (DQ_TYPE_DICT_UTF8): the row pass of dq_dict.hip, not a ColVariant.  A dictionary column's
+// tasks are ColTasks whose `variant` is kDictVariant (they sort after every column-pass variant and launch
+// together as one dq_dict_scan, timer kDictTimer) and whose `arg` says what they accumulate.  ScanCols carries
+// the int32 indices (values), the indices' validity and the entry table (offsets); DictSizes the table lengths.
+constexpr int32_t kDictVariant = kNumVariants;
+constexpr int kDictTimer = 4;                 // dq_plan_kernel_time id of the dictionary row pass
+constexpr int32_t kDictArgHll = 1, kDictArgDtype = 2;
+// Entry word (dq_dict_entries, dqscan.h): what the row pass needs of one dictionary entry.
+constexpr uint32_t kDictIdxBits = 9, kDictPwShift = 9, kDictPwBits = 6, kDictClassShift = 15, kDictClassBits = 3;
+constexpr uint32_t kDictNonNull = 1u << 18;   // bits 19..31: reserved, 0
+// tables of at most this many entries are staged in LDS by every workgroup of the row pass (DESIGN "Dictionary columns")
+constexpr int32_t kDictLdsEntries = 2048;
+struct DictSizes {
+  int32_t n[kMaxCols];  // entries of column c's table (0 for other columns)
+};
+
 struct ScanBitmaps {
   uint64_t* where_bits[kMaxWhere];
   int64_t* rare_rows;  // per column task: the rows the string pass's fast path skipped since the reset

@@ -17,6 +17,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <atomic>
+#include <climits>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -86,7 +88,46 @@ struct Piece {
   int64_t base = 0;        // kinds 1, 2
   int shift = 0;           // kind 3 (1..7)
   int64_t src_bytes = 0;   // kind 3: readable source bytes
+  // kind 4: dictionary indices widened to int32 and range-checked (dq_dict_check_indices' loop)
+  int idx_type = 0;                  // DQ_TYPE_I8 / I16 / I32, negative: unsigned
+  int64_t n_entries = 0;
+  const uint8_t* valid = nullptr;    // the rows' bitmap (row 0 at bit valid_bit) or NULL
+  int valid_bit = 0;
+  std::atomic<int64_t>* bad = nullptr;  // the lowest offending row, or INT64_MAX
 };
+
+// Rows [r0, r1) of a dictionary index array of `type` widened to int32 (out may be NULL) and checked against
+// [0, n_entries) where the row's validity bit (bit r + bit of `validity`, NULL: every row) is set; a NULL row's
+// index is written 0.  Returns the first offending row (its index in *bad_value), or -1.
+int64_t widen_check(int type, const void* src, int64_t r0, int64_t r1, const uint8_t* validity, int bit,
+                    int64_t n_entries, int32_t* out, int64_t* bad_value) {
+  auto run = [&](auto tag) -> int64_t {
+    using T = decltype(tag);
+    const char* p = static_cast<const char*>(src);
+    for (int64_t r = r0; r < r1; ++r) {
+      T t;
+      std::memcpy(&t, p + r * (int64_t)sizeof(T), sizeof(T));
+      const int64_t v = (int64_t)t, b = r + bit;
+      const bool valid = !validity || ((validity[b >> 3] >> (b & 7)) & 1);
+      if (valid && (v < 0 || v >= n_entries)) {
+        if (bad_value) *bad_value = v;
+        return r;
+      }
+      if (out) out[r] = valid ? (int32_t)v : 0;
+    }
+    return -1;
+  };
+  switch (type) {
+    case DQ_TYPE_I8: return run(int8_t{});
+    case DQ_TYPE_I16: return run(int16_t{});
+    case DQ_TYPE_I32: return run(int32_t{});
+    case -DQ_TYPE_I8: return run(uint8_t{});
+    default: return run(uint16_t{});  // -DQ_TYPE_I16 (index_type_ok)
+  }
+}
+bool index_type_ok(int t) {
+  return t == DQ_TYPE_I8 || t == DQ_TYPE_I16 || t == DQ_TYPE_I32 || t == -DQ_TYPE_I8 || t == -DQ_TYPE_I16;
+}
 
 void copy_part(const Piece& p, int64_t a, int64_t b) {  // destination bytes [a, b) of piece p
   switch (p.kind) {
@@ -109,6 +150,16 @@ void copy_part(const Piece& p, int64_t a, int64_t b) {  // destination bytes [a,
         std::memcpy(p.dst + 8 * i, &v, 8);
       }
       break;
+    case 4: {
+      int64_t v = 0;
+      const int64_t r = widen_check(p.idx_type, p.src, a / 4, b / 4, p.valid, p.valid_bit, p.n_entries,
+                                    reinterpret_cast<int32_t*>(p.dst), &v);
+      if (r >= 0) {
+        int64_t cur = p.bad->load();
+        while (r < cur && !p.bad->compare_exchange_weak(cur, r)) {}
+      }
+      break;
+    }
     default: {
       const uint8_t* src = reinterpret_cast<const uint8_t*>(p.src);
       for (int64_t i = a; i < b; ++i) {
@@ -237,6 +288,59 @@ dq_status dq_arrow_import(const struct ArrowSchema* schema, const struct ArrowAr
   return DQ_OK;
 }
 
+dq_status dq_arrow_import_dictionary(const struct ArrowSchema* schema, const struct ArrowArray* array,
+                                     dq_host_column* indices, dq_host_column* dictionary) {
+  const char* me = "dq_arrow_import_dictionary";
+  if (!schema || !array || !indices || !dictionary) return set_error(DQ_E_INVALID, "%s: bad argument", me);
+  if (!schema->release || !array->release) return set_error(DQ_E_INVALID, "%s: released Arrow structure", me);
+  if (!schema->dictionary || !array->dictionary) return set_error(DQ_E_INVALID, "%s: not a dictionary-encoded array", me);
+  if (schema->n_children != 0 || array->n_children != 0) return set_error(DQ_E_UNSUPPORTED, "%s: nested Arrow array", me);
+  const char* f = schema->format ? schema->format : "";
+  int32_t itype = 0, is_unsigned = 0;
+  if (std::strcmp(f, "c") == 0) itype = DQ_TYPE_I8;
+  else if (std::strcmp(f, "s") == 0) itype = DQ_TYPE_I16;
+  else if (std::strcmp(f, "i") == 0) itype = DQ_TYPE_I32;
+  else if (std::strcmp(f, "C") == 0) itype = DQ_TYPE_I8, is_unsigned = 1;
+  else if (std::strcmp(f, "S") == 0) itype = DQ_TYPE_I16, is_unsigned = 1;
+  else return set_error(DQ_E_UNSUPPORTED, "%s: dictionary indices of Arrow format '%s' (c, s, i, C, S)", me, f);
+  const char* df = schema->dictionary->format ? schema->dictionary->format : "";
+  if (std::strcmp(df, "u") != 0 && std::strcmp(df, "U") != 0)
+    return set_error(DQ_E_UNSUPPORTED, "%s: dictionary values of Arrow format '%s' (u, U)", me, df);
+  // the values: an ordinary string array (dq_arrow_import refuses a nested dictionary and honours a slice)
+  dq_host_column d{};
+  if (dq_status s = dq_arrow_import(schema->dictionary, array->dictionary, &d)) return s;
+  // the indices: the fixed-width array the format names, without the dictionary members
+  struct ArrowSchema is = *schema;
+  struct ArrowArray ia = *array;
+  is.dictionary = nullptr;
+  ia.dictionary = nullptr;
+  is.format = itype == DQ_TYPE_I8 ? "c" : itype == DQ_TYPE_I16 ? "s" : "i";
+  dq_host_column x{};
+  if (dq_status s = dq_arrow_import(&is, &ia, &x)) return s;
+  // the index column as dq_upload takes it: DQ_TYPE_DICT_UTF8, 4 bytes per row on the device, the source width
+  // in `reserved` (dq_dict_check_indices' type code: negative = unsigned), the entry count in `offset_base`
+  x.reserved = is_unsigned ? -itype : itype;
+  x.type = DQ_TYPE_DICT_UTF8;
+  x.value_bytes = 4 * x.n_rows;
+  x.offset_base = d.n_rows;
+  *indices = x;
+  *dictionary = d;
+  return DQ_OK;
+}
+
+dq_status dq_dict_check_indices(int32_t index_type, const void* indices, int64_t n, const uint8_t* validity,
+                                int32_t validity_bit, int64_t n_entries, int32_t* out) {
+  if (n < 0 || n_entries < 0 || validity_bit < 0 || validity_bit > 7 || (n > 0 && !indices))
+    return set_error(DQ_E_INVALID, "dq_dict_check_indices: bad argument");
+  if (!index_type_ok(index_type)) return set_error(DQ_E_UNSUPPORTED, "dq_dict_check_indices: index type %d", index_type);
+  int64_t v = 0;
+  const int64_t r = widen_check(index_type, indices, 0, n, validity, validity_bit, n_entries, out, &v);
+  if (r >= 0)
+    return set_error(DQ_E_INVALID, "dictionary index %lld at row %lld is outside the dictionary's %lld entries",
+                     (long long)v, (long long)r, (long long)n_entries);
+  return DQ_OK;
+}
+
 dq_status dq_uploader_create(int32_t device, int32_t n_slots, int64_t slot_bytes, int32_t host_threads,
                              dq_uploader** out) {
   if (!out || n_slots < 1 || n_slots > 8 || slot_bytes <= 0) return set_error(DQ_E_INVALID, "dq_uploader_create: bad argument");
@@ -281,6 +385,8 @@ dq_status dq_upload(dq_uploader* u, const dq_host_column* cols, int32_t n_cols, 
     const dq_host_column& h = cols[c];
     if (h.validity_bit < 0 || h.validity_bit > 7 || h.offset_base < 0)
       return set_error(DQ_E_INVALID, "dq_upload: column %d: bad slice rebase", c);
+    if (h.type == DQ_TYPE_DICT_UTF8 && (!index_type_ok(h.reserved) || h.offsets || h.value_bytes != 4 * h.n_rows))
+      return set_error(DQ_E_INVALID, "dq_upload: column %d: not a dictionary index column of dq_arrow_import_dictionary", c);
     const void* src[3] = {h.values, h.validity, h.offsets};
     const int64_t len[3] = {h.value_bytes, h.validity_bytes, h.offset_bytes};
     for (int k = 0; k < 3; ++k) {
@@ -297,6 +403,8 @@ dq_status dq_upload(dq_uploader* u, const dq_host_column* cols, int32_t n_cols, 
   // the slot's previous DMA must have drained the pinned buffer before the CPU overwrites it
   if (u->used[(size_t)s] && (e = hipEventSynchronize(u->copied[(size_t)s])) != hipSuccess)
     return set_error(DQ_E_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
+  std::vector<std::atomic<int64_t>> bad((size_t)std::max(1, n_cols));
+  for (auto& b : bad) b.store(INT64_MAX);
   for (int32_t c = 0; c < n_cols; ++c) {
     const dq_host_column& h = cols[c];
     const void* src[3] = {h.values, h.validity, h.offsets};
@@ -304,6 +412,14 @@ dq_status dq_upload(dq_uploader* u, const dq_host_column* cols, int32_t n_cols, 
     for (int k = 0; k < 3; ++k) {
       if (pos[3 * (size_t)c + k] < 0) continue;
       Piece p{u->pinned[(size_t)s] + pos[3 * (size_t)c + k], static_cast<const char*>(src[k]), len[k]};
+      if (k == 0 && h.type == DQ_TYPE_DICT_UTF8) {  // narrow indices -> int32, validated in the same loop
+        p.kind = 4;
+        p.idx_type = h.reserved;
+        p.n_entries = h.offset_base;
+        p.valid = h.validity;
+        p.valid_bit = h.validity_bit;
+        p.bad = &bad[(size_t)c];
+      }
       if ((k == 1 || (k == 0 && h.type == DQ_TYPE_BOOL)) && h.validity_bit) {  // bitmaps of a slice
         p.kind = 3;
         p.shift = h.validity_bit;
@@ -317,6 +433,15 @@ dq_status dq_upload(dq_uploader* u, const dq_host_column* cols, int32_t n_cols, 
     }
   }
   parallel_copy(pieces, u->threads);
+  for (int32_t c = 0; c < n_cols; ++c) {  // an index outside its dictionary: nothing is uploaded or scanned
+    const int64_t r = bad[(size_t)c].load();
+    if (r == INT64_MAX) continue;
+    int64_t v = 0;
+    (void)widen_check(cols[c].reserved, cols[c].values, r, r + 1, cols[c].validity, cols[c].validity_bit,
+                      cols[c].offset_base, nullptr, &v);
+    return set_error(DQ_E_INVALID, "dq_upload: column %d: dictionary index %lld at row %lld is outside the dictionary's "
+                     "%lld entries", c, (long long)v, (long long)r, (long long)cols[c].offset_base);
+  }
   // the scan that last read the device slot must have passed its release before the DMA overwrites it
   if (u->used[(size_t)s] && (e = hipStreamWaitEvent(u->copy, u->released[(size_t)s], 0)) != hipSuccess)
     return set_error(DQ_E_HIP, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));

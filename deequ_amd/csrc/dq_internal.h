@@ -50,5 +50,10 @@ dq_status state_metric(const dq_state& s, double& out);
 int64_t state_to_bytes(const dq_state& s, uint8_t* buf, int64_t cap);
 dq_status state_from_bytes(int32_t op, const uint8_t* buf, int64_t len, dq_state& o);
 int32_t murmur3_string_hash_utf8(const char* s, uint32_t seed);
+// dq_take_rows' string gather (dq_schema.hip), shared with dq_dict_decode: out string r = src string index[r] (an
+// index outside src's n_rows: the empty string).  Synchronises st.
+dq_status take_strings(bool large, const dq_column_view* src, int64_t n_rows, const int64_t* index, int64_t n_selected,
+                       void* out_values, int64_t values_capacity, void* out_offsets, int64_t* data_bytes,
+                       hipStream_t st, const char* me);
 
 }  // namespace dq

@@ -71,6 +71,9 @@ hipError_t launch_finalize(int32_t ncol, int32_t nranges_col, const ColPartial* 
                            int32_t npair, int32_t nranges_pair, const CorrPartial* pair_part, CorrPartial* pair_acc,
                            int32_t has_pred, int32_t nranges_pred, const PredPartial* pred_part, PredPartial* pred_acc, const FinRanges& fr, int64_t* rare_dev, int64_t* rare_host,
                            int32_t nhll, const uint32_t* hll_acc, uint32_t* hll_floor, hipStream_t st);
+hipError_t launch_dict_scan(const ColTask* tasks, int32_t ntasks, int32_t part_base, const ScanCols& cols,
+                            const DictSizes& sizes, const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range,
+                            int32_t nranges, ColPartial* partials, uint32_t* hll_acc, hipStream_t stream);
 hipError_t launch_init_acc(ColPartial* col_acc, int32_t ncol, CorrPartial* pair_acc, int32_t npair, int64_t* rare_dev,
                            hipStream_t st);
 
@@ -105,11 +108,14 @@ static bool is_numeric(int32_t t) {
 static bool is_integral(int32_t t) { return t == DQ_TYPE_I64 || t == DQ_TYPE_I32 || t == DQ_TYPE_I16 || t == DQ_TYPE_I8; }
 static bool is_floating(int32_t t) { return t == DQ_TYPE_F64 || t == DQ_TYPE_F32; }
 static bool is_string(int32_t t) { return t == DQ_TYPE_UTF8 || t == DQ_TYPE_LARGE_UTF8; }
+static bool is_dict(int32_t t) { return t == DQ_TYPE_DICT_UTF8; }
+// the column types a plan takes: type_valid's, and a dictionary-encoded string column
+static bool plan_type_valid(int32_t t) { return type_valid(t) || is_dict(t); }
 static int32_t kind_of(int32_t t) {
   switch (t) {
     case DQ_TYPE_F64: return CK_F64;
     case DQ_TYPE_I64: case DQ_TYPE_TIMESTAMP: return CK_I64;
-    case DQ_TYPE_I32: case DQ_TYPE_DATE32: return CK_I32;
+    case DQ_TYPE_I32: case DQ_TYPE_DATE32: case DQ_TYPE_DICT_UTF8: return CK_I32;  // (a dictionary column's indices)
     case DQ_TYPE_F32: return CK_F32;
     case DQ_TYPE_I16: return CK_I16;
     case DQ_TYPE_I8: return CK_I8;
@@ -128,7 +134,7 @@ static int32_t pair_kind(int32_t t) {
 // algorithmic bytes per row (x1000) of a column's value (or UTF8 offset) buffer
 static int64_t value_bytes_x1000(int32_t t) {
   switch (t) {
-    case DQ_TYPE_I32: case DQ_TYPE_F32: case DQ_TYPE_DATE32: case DQ_TYPE_UTF8: return 4000;
+    case DQ_TYPE_I32: case DQ_TYPE_F32: case DQ_TYPE_DATE32: case DQ_TYPE_UTF8: case DQ_TYPE_DICT_UTF8: return 4000;
     case DQ_TYPE_I16: return 2000;
     case DQ_TYPE_I8: return 1000;
     case DQ_TYPE_BOOL: return 125;
@@ -275,6 +281,8 @@ struct Lowering {
   }
   dq_status check_col(int32_t c) {
     if (c < 0 || c >= (int32_t)schema->size()) return set_error(DQ_E_INVALID, "predicate column %d out of range", c);
+    if (is_dict((*schema)[c].type))  // (every atom's column passes here)
+      return set_error(DQ_E_UNSUPPORTED, "predicate over dictionary-encoded column %d: decode it (dq_dict_decode)", c);
     return DQ_OK;
   }
   void push_const(int nr) {
@@ -644,6 +652,7 @@ struct dq_plan {
   struct Group { int32_t variant, first, count; };
   std::vector<Group> groups;              // one column-scan launch per variant group
   std::vector<Group> pred_fused_groups;   // the predicate kernel's HLL tasks as column-pass launches (interpreter)
+  int32_t dict_first = 0, dict_count = 0; // the dictionary columns' tasks (variant kDictVariant): one dq_dict_scan launch
   std::vector<PairTask> pair_tasks;      // sorted by pair group
   std::vector<PairWG> pair_wgs;          // Correlation pass workgroup tasks (dq_pair.hip), moments fused
   int32_t n_fused = 0;                    // column tasks computed by the pair pass (sorted last)
@@ -980,7 +989,15 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
       case DQ_OP_COMPLETENESS: {
         if (dq_status st = need_col(s.col_a)) return st;
         o.col_type = p->schema[s.col_a].type;
-        if (where_slot >= 0) {
+        if (is_dict(o.col_type)) {
+          // a dictionary row is NULL also when its entry is: the row pass counts the non-null selected rows (under
+          // the `where` bitmap), whatever the column's nullable flag says; the predicate pass only counts `where`
+          int32_t bm;
+          if (dq_status st = bitmap(where_slot, bm)) return st;
+          if (dq_status st = col_task(s.col_a, bm, false, false, o.col_task)) return st;
+          if (where_slot >= 0)
+            if (dq_status st = counter(where_slot, -1, o.ctr_b)) return st;
+        } else if (where_slot >= 0) {
           int32_t nn;
           if (dq_status st = notnull_root(s.col_a, nn)) return st;
           if (dq_status st = counter(nn, where_slot, o.ctr_a)) return st;
@@ -1014,6 +1031,8 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
         if (dq_status st = need_col(s.col_a)) return st;
         o.col_type = p->schema[s.col_a].type;
         bool hll = s.op == DQ_OP_APPROX_COUNT_DISTINCT;
+        if (!hll && is_dict(o.col_type))
+          return set_error(DQ_E_UNSUPPORTED, "spec %zu: op %d on dictionary-encoded column %d", i, s.op, s.col_a);
         if (!hll && !is_numeric(o.col_type))  // Preconditions.isNumeric (Analyzer.scala:322-334)
           return set_error(DQ_E_TYPE, "spec %zu: column %d is not numeric", i, s.col_a);
         int32_t bm;
@@ -1029,13 +1048,15 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
         // only floating-point, decimal and string values need classifying: an integral value's string always matches
         // INTEGRAL, a boolean's ("true" / "false") BOOLEAN, a date's / timestamp's ("2020-01-31 ...") STRING -- the
         // selected-row count suffices (dq_finish puts it in the type's class)
-        const bool classify = is_floating(o.col_type) || is_string(o.col_type) || is_decimal(o.col_type);
+        const bool classify = is_floating(o.col_type) || is_string(o.col_type) || is_decimal(o.col_type) || is_dict(o.col_type);
         if (dq_status st = col_task(s.col_a, bm, false, false, o.col_task, classify)) return st;
         break;
       }
       case DQ_OP_CORRELATION: {
         if (dq_status st = need_col(s.col_a)) return st;
         if (dq_status st = need_col(s.col_b)) return st;
+        if (is_dict(p->schema[s.col_a].type) || is_dict(p->schema[s.col_b].type))
+          return set_error(DQ_E_UNSUPPORTED, "spec %zu: Correlation on a dictionary-encoded column", i);
         if (!is_numeric(p->schema[s.col_a].type) || !is_numeric(p->schema[s.col_b].type))
           return set_error(DQ_E_TYPE, "spec %zu: Correlation needs numeric columns", i);
         int32_t bm;
@@ -1066,6 +1087,11 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
     const bool stats = col_task_needs[t].stats, hll = col_task_needs[t].hll, dtype = col_task_needs[t].dtype;
     int32_t type = p->schema[ct.col].type;
     if (hll) ct.hll_slot = p->n_hll++;
+    if (is_dict(type)) {  // the dictionary row pass (dq_dict.hip), not a column-pass variant
+      ct.variant = kDictVariant;
+      ct.arg = (hll ? kDictArgHll : 0) | (dtype ? kDictArgDtype : 0);
+      continue;
+    }
     if (is_decimal(type)) ct.arg = DQ_DECIMAL_PRECISION(type) | DQ_DECIMAL_SCALE(type) << 8;
     // the variant the table (dq_device.h kVariants) has for the column's kind and the task's needs.  (TimestampType
     // is CK_I64: hashLong of the micros; DateType CK_I32: hashInt of the days.)
@@ -1141,6 +1167,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
       std::vector<int32_t> tasks;
       for (size_t t = 0; t < p->col_tasks.size() && hll.size() < 8; ++t) {
         const ColTask& ct = p->col_tasks[t];
+        if (ct.variant == kDictVariant) continue;
         const int32_t k = cv_kind(ct.variant);  // HLL-only tasks of the kinds the generated kernel hashes
         if (ct.where >= 0 || cv_stats(ct.variant) || !cv_hll(ct.variant) || (k != CK_F64 && k != CK_I64 && k != CK_I32))
           continue;
@@ -1272,6 +1299,10 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
     p->pair_fused_first = p->pred_fused_first - p->pair_fused_count;
     for (int32_t k = 0; k < (int32_t)p->col_tasks.size(); ++k) {
       if (fused[order[k]]) break;  // fused tasks sort last: their partials come from the pair / predicate pass
+      if (p->col_tasks[k].variant == kDictVariant) {  // (after every column-pass variant)
+        if (p->dict_count++ == 0) p->dict_first = k;
+        continue;
+      }
       if (p->groups.empty() || p->groups.back().variant != p->col_tasks[k].variant)
         p->groups.push_back({p->col_tasks[k].variant, k, 0});
       p->groups.back().count++;
@@ -1288,7 +1319,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   std::vector<int> need_values(ncols, 0), need_validity(ncols, 0);
   for (const ColTask& ct : p->col_tasks) {
     need_validity[ct.col] = 1;
-    if (cv_kind(ct.variant) != CK_NONE) need_values[ct.col] = 1;
+    if (ct.variant == kDictVariant || cv_kind(ct.variant) != CK_NONE) need_values[ct.col] = 1;
   }
   for (const PairTask& pt : p->pair_tasks) {
     need_values[pt.col_x] = need_values[pt.col_y] = 1;
@@ -1330,7 +1361,8 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
     p->pred_bytes_x1000 = bytes_of(pv, pn);
     p->pair_bytes_x1000 = bytes_of(qv, qn);
   }
-  p->launches_per_scan = (p->has_pred ? 1 : 0) + (int32_t)p->groups.size() + (p->pair_wgs.empty() ? 0 : 1) +
+  p->launches_per_scan = (p->has_pred ? 1 : 0) + (int32_t)p->groups.size() + (p->dict_count ? 1 : 0) +
+                         (p->pair_wgs.empty() ? 0 : 1) +
                          ((p->col_tasks.size() + p->pair_tasks.size()) ? 1 : 0);
 
   if (p->host_only) return DQ_OK;
@@ -1561,6 +1593,10 @@ static std::string explain_text(const dq_plan& plan) {
     std::snprintf(line, sizeof line, "column pass: variant %d, %d task(s)\n", g.variant, g.count);
     t += line;
   }
+  if (plan.dict_count > 0) {
+    std::snprintf(line, sizeof line, "dictionary pass: %d task(s)\n", plan.dict_count);
+    t += line;
+  }
   std::snprintf(line, sizeof line, "pair pass: %zu pair(s), %zu workgroup task(s)\n", plan.pair_tasks.size(),
                 plan.pair_wgs.size());
   t += line;
@@ -1646,7 +1682,7 @@ dq_status dq_plan_create_opts(const dq_analyzer_spec* specs, int32_t n_specs, co
     return set_error(DQ_E_INVALID, "dq_plan_create: bad schema (at most %d columns)", kMaxSchemaCols);
   if (n_pred < 0 || (n_pred > 0 && !pred_pool)) return set_error(DQ_E_INVALID, "dq_plan_create: bad predicate pool");
   for (int32_t c = 0; c < n_cols; ++c)
-    if (!type_valid(schema[c].type))
+    if (!plan_type_valid(schema[c].type))
       return set_error(DQ_E_TYPE, "dq_plan_create: column %d has unknown type %d", c, schema[c].type);
   int ndev = 0;
   DQ_HIP(hipGetDeviceCount(&ndev));
@@ -1730,7 +1766,12 @@ dq_status dq_plan_set_stream(dq_plan* p, void* hip_stream) {
 // dq_scan's contract for one column view (dqscan.h dq_column_view)
 static dq_status check_view(const dq_column_desc& cd, const dq_column_view& v, int32_t c, int64_t n_rows) {
   const int32_t t = cd.type;
-  if (v.reserved != 0) return set_error(DQ_E_INVALID, "dq_scan: column %d reserved field must be 0", c);
+  if (is_dict(t)) {  // reserved = the number of entries, offsets = the entry words
+    if (v.reserved < 0 || v.reserved > INT32_MAX)
+      return set_error(DQ_E_INVALID, "dq_scan: dictionary column %d has %lld entries", c, (long long)v.reserved);
+    if ((v.reserved > 0 && !v.offsets) || ((uintptr_t)v.offsets & 3) != 0)
+      return set_error(DQ_E_INVALID, "dq_scan: dictionary column %d needs a 4-byte aligned entry table", c);
+  } else if (v.reserved != 0) return set_error(DQ_E_INVALID, "dq_scan: column %d reserved field must be 0", c);
   if (n_rows > 0 && !v.values) return set_error(DQ_E_INVALID, "dq_scan: column %d has no values buffer", c);
   if (((uintptr_t)v.values & 15) != 0)
     return set_error(DQ_E_INVALID, "dq_scan: column %d values buffer must be 16-byte aligned", c);
@@ -1776,10 +1817,12 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
     return DQ_OK;
   }
   ScanCols sc{};
+  DictSizes dsz{};
   for (int32_t c = 0; c < ncols; ++c)
     if (dq_status s = check_view(p->schema[c], cols[c], c, n_rows)) return s;
   for (int32_t c = 0; c < ncols; ++c) {
     const dq_column_view& v = cols[c];
+    if (is_dict(p->schema[c].type)) dsz.n[c] = (int32_t)v.reserved;
     sc.values[c] = v.values;
     sc.validity[c] = p->schema[c].nullable ? reinterpret_cast<const uint32_t*>(v.validity) : nullptr;
     sc.offsets[c] = v.offsets;
@@ -1982,6 +2025,13 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
         }))
       return s;
   }
+  if (p->dict_count > 0) {  // every dictionary column task in one launch, on the scan's default ranges
+    if (dq_status s = timed(p, kDictTimer, p->stream, [&] {
+          return launch_dict_scan(p->d_col_tasks + p->dict_first, p->dict_count, p->dict_first, sc, dsz, bm, n_rows,
+                                  rpr_col, nr_col, p->d_col_part, p->d_hll_acc, p->stream);
+        }))
+      return s;
+  }
   if (!p->pair_wgs.empty()) {
     // the LDS-ring path's 16-byte DMA needs 16-byte aligned fp64 columns (dq_scan's contract; checked above)
     const bool ring = pair_ring;
@@ -2086,7 +2136,7 @@ dq_status dq_finish(dq_plan* p, dq_state* out) {
         break;
       case DQ_OP_COMPLETENESS:
         if (o.has_where) {
-          s.u.ratio.num_matches = pred.t[o.ctr_a];
+          s.u.ratio.num_matches = o.ctr_a >= 0 ? pred.t[o.ctr_a] : c->count;  // (c: a dictionary column's row pass)
           s.u.ratio.count = pred.t[o.ctr_b];
           s.has_value[0] = rows > 0;
           s.has_value[1] = pred.nn[o.ctr_b] > 0;
@@ -2177,7 +2227,7 @@ dq_status dq_finish(dq_plan* p, dq_state* out) {
       case DQ_OP_DATATYPE: {  // StatefulDataType: NULL (incl. where-false), FRACTIONAL, INTEGRAL, BOOLEAN, STRING
         auto& d = s.u.dtype;
         d.num_null = rows - c->count;
-        if (o.col_type == DQ_TYPE_UTF8 || o.col_type == DQ_TYPE_LARGE_UTF8) {
+        if (is_string(o.col_type) || is_dict(o.col_type)) {
           d.num_fractional = c->isum;
           d.num_integral = c->nan_count;
           d.num_boolean = (int64_t)c->sum;
@@ -2317,7 +2367,7 @@ int64_t dq_plan_explain(const dq_analyzer_spec* specs, int32_t n_specs, const dq
   for (int32_t k = 0; k < n_patterns; ++k)
     if (!patterns[k]) return set_error(DQ_E_INVALID, "dq_plan_explain: pattern %d is NULL", k);
   for (int32_t c = 0; c < n_cols; ++c)
-    if (!type_valid(schema[c].type))
+    if (!plan_type_valid(schema[c].type))
       return set_error(DQ_E_TYPE, "dq_plan_explain: column %d has unknown type %d", c, schema[c].type);
   if (cap < 0 || (cap > 0 && !out)) return set_error(DQ_E_INVALID, "dq_plan_explain: bad output buffer");
   std::unique_ptr<dq_plan> holder(new dq_plan());

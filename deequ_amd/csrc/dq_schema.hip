@@ -273,6 +273,39 @@ struct dq_schema_plan {
   }
 };
 
+namespace dq {
+// The string gather of dq_take_rows, also dq_dict_decode's (dq_dict.hip): string r of the output is string index[r] of
+// src's n_rows (an index outside them: the empty string); the same row may be taken any number of times.
+dq_status take_strings(bool large, const dq_column_view* src, int64_t n_rows, const int64_t* index, int64_t n_selected,
+                       void* out_values, int64_t values_capacity, void* out_offsets, int64_t* data_bytes,
+                       hipStream_t st, const char* me) {
+  const unsigned grid1 = grid_for(n_selected + 1, kTakeBlock);
+  if (!large && n_selected >= INT32_MAX) return set_error(DQ_E_INVALID, "%s: UTF8 chunk of %lld rows", me, (long long)n_selected);
+  DevPtr<int64_t> lens;
+  DevPtr<void> temp;
+  DQ_HIP(lens.alloc((size_t)(n_selected + 1)));
+  DQ_HIP(temp.alloc(prim::scan_temp_bytes(n_selected + 1) + 16));
+  int64_t* const dl = lens.get();
+  if (large) hipLaunchKernelGGL(dq_take_lengths<int64_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const int64_t*>(src->offsets), index, n_selected, n_rows, dl);
+  else hipLaunchKernelGGL(dq_take_lengths<int32_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const int32_t*>(src->offsets), index, n_selected, n_rows, dl);
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(prim::exclusive_sum_i64(dl, dl, n_selected + 1, temp.get(), st));
+  int64_t total = 0;
+  DQ_HIP(hipMemcpyAsync(&total, dl + n_selected, 8, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  if (data_bytes) *data_bytes = total;
+  if (!large && total > INT32_MAX) return set_error(DQ_E_INVALID, "%s: %lld bytes do not fit UTF8 offsets", me, (long long)total);
+  if (out_values && values_capacity < total)
+    return set_error(DQ_E_INVALID, "%s: %lld value bytes for %lld", me, (long long)values_capacity, (long long)total);
+  // (out_values NULL: the sizing call -- offsets and *data_bytes only)
+  if (large) hipLaunchKernelGGL(dq_take_strings<int64_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const uint32_t*>(src->values), static_cast<const int64_t*>(src->offsets), index, dl, n_selected, n_rows, static_cast<int64_t*>(out_offsets), static_cast<uint8_t*>(out_values));
+  else hipLaunchKernelGGL(dq_take_strings<int32_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const uint32_t*>(src->values), static_cast<const int32_t*>(src->offsets), index, dl, n_selected, n_rows, static_cast<int32_t*>(out_offsets), static_cast<uint8_t*>(out_values));
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(hipStreamSynchronize(st));
+  return DQ_OK;
+}
+}  // namespace dq
+
 extern "C" {
 
 dq_status dq_schema_plan_create(const dq_schema_column* defs, int32_t n_defs, dq_schema_plan** out) {
@@ -494,7 +527,7 @@ dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, 
     return set_error(DQ_E_INVALID, "%s: misaligned buffer", me);
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   DQ_HIP(hipSetDevice(device));
-  const unsigned grid = grid_for(n_selected, kTakeBlock), grid1 = grid_for(n_selected + 1, kTakeBlock);
+  const unsigned grid = grid_for(n_selected, kTakeBlock);
   const unsigned grid_bits = grid_for(((n_selected + 63) >> 6) * 64, kTakeBlock);
   if (out_validity) {
     hipLaunchKernelGGL(dq_take_bits, dim3(grid_bits), dim3(kTakeBlock), 0, st, reinterpret_cast<const uint32_t*>(src->validity),
@@ -523,29 +556,7 @@ dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, 
     DQ_HIP(hipStreamSynchronize(st));
     return DQ_OK;
   }
-  if (!large && n_selected >= INT32_MAX) return set_error(DQ_E_INVALID, "%s: UTF8 chunk of %lld rows", me, (long long)n_selected);
-  DevPtr<int64_t> lens;
-  DevPtr<void> temp;
-  DQ_HIP(lens.alloc((size_t)(n_selected + 1)));
-  DQ_HIP(temp.alloc(prim::scan_temp_bytes(n_selected + 1) + 16));
-  int64_t* const dl = lens.get();
-  if (large) hipLaunchKernelGGL(dq_take_lengths<int64_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const int64_t*>(src->offsets), index, n_selected, n_rows, dl);
-  else hipLaunchKernelGGL(dq_take_lengths<int32_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const int32_t*>(src->offsets), index, n_selected, n_rows, dl);
-  DQ_HIP(hipGetLastError());
-  DQ_HIP(prim::exclusive_sum_i64(dl, dl, n_selected + 1, temp.get(), st));
-  int64_t total = 0;
-  DQ_HIP(hipMemcpyAsync(&total, dl + n_selected, 8, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  if (data_bytes) *data_bytes = total;
-  if (!large && total > INT32_MAX) return set_error(DQ_E_INVALID, "%s: %lld bytes do not fit UTF8 offsets", me, (long long)total);
-  if (out_values && values_capacity < total)
-    return set_error(DQ_E_INVALID, "%s: %lld value bytes for %lld", me, (long long)values_capacity, (long long)total);
-  // (out_values NULL: the sizing call -- offsets and *data_bytes only)
-  if (large) hipLaunchKernelGGL(dq_take_strings<int64_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const uint32_t*>(src->values), static_cast<const int64_t*>(src->offsets), index, dl, n_selected, n_rows, static_cast<int64_t*>(out_offsets), static_cast<uint8_t*>(out_values));
-  else hipLaunchKernelGGL(dq_take_strings<int32_t>, dim3(grid1), dim3(kTakeBlock), 0, st, static_cast<const uint32_t*>(src->values), static_cast<const int32_t*>(src->offsets), index, dl, n_selected, n_rows, static_cast<int32_t*>(out_offsets), static_cast<uint8_t*>(out_values));
-  DQ_HIP(hipGetLastError());
-  DQ_HIP(hipStreamSynchronize(st));
-  return DQ_OK;
+  return take_strings(large, src, n_rows, index, n_selected, out_values, values_capacity, out_offsets, data_bytes, st, me);
 }
 
 }  // extern "C"

@@ -193,6 +193,9 @@ def _views(chunks, columns: Sequence[str]):
 
 def build_frequencies(data, columns: Sequence[str]) -> "FrequenciesAndNumRows":
     """computeFrequencies(data, columns) + numRows = data.count() on the GPU."""
+    from .table import plain_utf8
+
+    data = plain_utf8(data)  # (dictionary-encoded string columns: read as the plain columns they stand for)
     import torch
 
     from .runner import _chunks
@@ -574,6 +577,9 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
                 from .metrics import UnsupportedOnGpuPathException
 
                 raise UnsupportedOnGpuPathException(f"{self}: a binning UDF runs in Spark, not on the GPU path")
+            from .table import plain_utf8
+
+            data = plain_utf8(data, [self.column])  # (the bins' values are rendered from the plain column)
             state = build_frequencies(data, [self.column])
             if aggregateWith is not None or saveStatesWith is not None:
                 state.materialize()  # once, before the merge and the first persist

@@ -26,7 +26,7 @@ from .table import Table, decimal_ps
 DEFAULT_CARDINALITY_THRESHOLD = 120
 NULL_FIELD_REPLACEMENT = "NullValue"  # Histogram.NullFieldReplacement
 MAX_COLUMNS_PER_CALL = 1024           # dq_cat_hist_build's column limit (include/dqscan.h)
-_STRING = ("utf8", "large_utf8")
+_STRING = ("utf8", "large_utf8", "dict_utf8")  # (a dictionary-encoded column is a StringType column)
 
 
 @dataclass(eq=True)
@@ -261,6 +261,9 @@ def compute_histograms(data, columns: Sequence[str]) -> Dict[str, Distribution]:
     """computeHistograms (:518-565) on the device: the Distribution of every target column from one fused pass (at
     most MAX_COLUMNS_PER_CALL columns per call); a column over the pass's capacity goes through build_frequencies and
     gives the same Distribution."""
+    from .table import plain_utf8
+
+    data = plain_utf8(data)  # (dictionary-encoded string columns: read as the plain columns they stand for)
     columns = list(columns)
     chunks = _chunks(data)
     schema = {name: dt for name, dt, _ in chunks[0].schema} if chunks else {}

@@ -23,11 +23,50 @@ from .analyzers import Analyzer, PlanBuilder, Preconditions, data_schema
 from .metrics import DoubleMetric, UnsupportedOnGpuPathException
 from .predicates import UnsupportedPredicate
 from .states import State
-from .table import Table
+from .table import Table, plain_utf8
 
 
 def _chunks(data) -> List[Table]:
     return [data] if isinstance(data, Table) else list(data)
+
+
+def dictionary_columns_to_decode(schema, analyzers: Sequence[Analyzer]) -> set:
+    """The dict_utf8 columns of `schema` that a run of `analyzers` reads as string bytes.  A column stays encoded (the
+    plan's dictionary row pass reads indices only) while the run refers to it only as the column of Completeness /
+    ApproxCountDistinct / DataType; any other reference -- a predicate or `where` atom, PatternMatch, a grouping
+    column, an analyzer with a device pass of its own -- needs the decoded plain column."""
+    from .analyzers import ApproxCountDistinct, Completeness, DataType
+    from .metrics import NoSuchColumnException
+
+    dict_cols = {c[0] for c in schema if c[1] == "dict_utf8"}
+    if not dict_cols:
+        return set()
+    as_plain = [(n, "utf8" if n in dict_cols else dt, nl) for n, dt, nl in schema]
+    decode = set()
+    for a in analyzers:
+        b = PlanBuilder(as_plain)
+        try:
+            if isinstance(a, (Completeness, ApproxCountDistinct, DataType)) and a.column in dict_cols:
+                b.pred(a.where)  # only its `where` reads other columns' values
+            elif getattr(a, "grouping", False):
+                b.columns.extend(a.groupingColumns() if hasattr(a, "groupingColumns") else [a.column])
+            else:
+                a._lower(b)
+        except (UnsupportedPredicate, NoSuchColumnException):
+            # the analyzer goes to the fallback set or fails its own way later; which columns its text names is
+            # not known here, so none of them may stay encoded
+            return dict_cols
+        decode |= dict_cols & set(b.columns)
+    return decode
+
+
+def route_dictionary_columns(data, analyzers: Sequence[Analyzer]):
+    """Where a run's analyzers meet its chunks' columns: the dict_utf8 columns the run reads as bytes
+    (dictionary_columns_to_decode) are replaced by their decoded plain columns for this run; the others keep their
+    dictionary view.  Nothing is refused.  Data without a dict_utf8 column comes back as it is, untouched."""
+    chunks = _chunks(data)
+    decode = dictionary_columns_to_decode(chunks[0].schema, analyzers) if chunks else set()
+    return plain_utf8(data, decode) if decode else data
 
 
 class ScanPlan:
@@ -41,6 +80,7 @@ class ScanPlan:
         import torch
 
         self.analyzers = list(analyzers)
+        self.schema = list(schema)
         b = PlanBuilder(schema)
         specs = (L.AnalyzerSpec * max(1, len(self.analyzers)))()
         for i, a in enumerate(self.analyzers):
@@ -172,7 +212,7 @@ def explain(analyzers: Sequence[Analyzer], schema, pred_pass: str = "auto") -> s
 
 def scan_results(data, analyzers: Sequence[Analyzer], pred_pass: str = "auto") -> List[L.State]:
     """Fused scan of all chunks -> raw aggregation-result slot sets, one per analyzer."""
-    chunks = _chunks(data)
+    chunks = _chunks(route_dictionary_columns(data, analyzers))
     plan = ScanPlan(analyzers, chunks[0].schema, pred_pass=pred_pass)
     try:
         for t in chunks:
@@ -277,6 +317,7 @@ class AnalysisRunner:
         if not all_analyzers:
             return AnalyzerContext.empty()
         schema = data_schema(data)
+        data = route_dictionary_columns(data, all_analyzers)  # (a decoded column is a StringType column too)
         passed, failures = [], {}
         for a in all_analyzers:
             err = Preconditions.findFirstFailing(schema, a.preconditions())

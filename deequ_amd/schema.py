@@ -293,6 +293,9 @@ class RowLevelSchemaValidator:
     def validate(data: Union[Table, Sequence[Table]], schema: RowLevelSchema) -> RowLevelSchemaValidationResult:
         """validate (:183-206).  `data`: a Table, or a sequence of chunk Tables of one layout, validated chunk by
         chunk (the result tables are then lists, one Table per chunk)."""
+        from .table import plain_utf8
+
+        data = plain_utf8(data)  # (dictionary-encoded string columns: read as the plain columns they stand for)
         single = isinstance(data, Table)
         chunks = [data] if single else list(data)
         if not chunks:

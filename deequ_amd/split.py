@@ -78,6 +78,9 @@ def random_split(data: Union[Table, Sequence[Table]], test_ratio: float, seed: O
     """(train, test) of a Table or of a sequence of chunk Tables (then two lists, one Table per chunk, zero-row chunks
     kept).  Chunk k's rows are numbered after the rows of the chunks before it.  seed=None draws one from `secrets`,
     as randomSplit without a seed draws its own; the seed used is on the result."""
+    from .table import plain_utf8
+
+    data = plain_utf8(data)  # (dictionary-encoded string columns: read as the plain columns they stand for)
     check_ratio(test_ratio)
     if seed is None:
         seed = secrets.randbits(64)

@@ -18,7 +18,8 @@ from . import _lib as L
 
 DTYPES = {"f64": L.TYPE_F64, "i64": L.TYPE_I64, "i32": L.TYPE_I32, "utf8": L.TYPE_UTF8,
           "large_utf8": L.TYPE_LARGE_UTF8, "f32": L.TYPE_F32, "i16": L.TYPE_I16, "i8": L.TYPE_I8,
-          "bool": L.TYPE_BOOL, "date32": L.TYPE_DATE32, "timestamp": L.TYPE_TIMESTAMP}
+          "bool": L.TYPE_BOOL, "date32": L.TYPE_DATE32, "timestamp": L.TYPE_TIMESTAMP,
+          "dict_utf8": L.TYPE_DICT_UTF8}
 # Preconditions.isNumeric (Analyzer.scala:322-334): ByteType .. DoubleType, and DecimalType ("decimal(p,s)")
 NUMERIC = ("f64", "i64", "i32", "f32", "i16", "i8")
 
@@ -84,9 +85,16 @@ class Column:
     offsets: Optional[object] = None
     nullable: bool = True
     data_bytes: int = 0            # UTF-8 payload bytes (for traffic accounting)
+    dictionary: Optional["Dictionary"] = None  # dict_utf8: values = int32 indices into it
 
     def view(self) -> L.ColumnView:
         v = L.ColumnView()
+        if self.dtype == "dict_utf8":  # dqscan.h: indices, their bitmap, the entry words, the number of entries
+            v.values = self.values.data_ptr()
+            v.validity = self.validity.data_ptr() if self.validity is not None else None
+            v.offsets = self.dictionary.entry_table().data_ptr()
+            v.reserved = self.dictionary.n_entries
+            return v
         v.values = self.values.data_ptr() if self.values is not None else None
         v.validity = self.validity.data_ptr() if self.validity is not None else None
         v.offsets = self.offsets.data_ptr() if self.offsets is not None else None
@@ -96,6 +104,93 @@ class Column:
     @property
     def type_code(self) -> int:
         return type_code(self.dtype)
+
+
+class Dictionary:
+    """The strings a dict_utf8 column's indices refer to: a device utf8 / large_utf8 Column of n_entries entries (an
+    entry may be NULL), shared by every column and chunk that uses it.  The entry table (dq_dict_entries) and the
+    decoded plain column of a given index column are built on first use and kept."""
+
+    entries_calls = 0  # dq_dict_entries launches of the process (tests count them)
+
+    def __init__(self, entries: Column):
+        if entries.dtype not in ("utf8", "large_utf8"):
+            raise ValueError("a dictionary holds utf8 / large_utf8 entries")
+        self.entries = entries
+        self.n_entries = entries.n_rows
+        self._table = None
+
+    def entry_table(self):
+        """uint32[n_entries] entry words on the device (include/dqscan.h dq_dict_entries)."""
+        if self._table is None:
+            import ctypes
+
+            torch = _torch()
+            dev = self.entries.values.device
+            t = torch.zeros(max(4, self.n_entries), dtype=torch.int32, device=dev)
+            view = self.entries.view()
+            with torch.cuda.device(dev):
+                L.check(L.lib.dq_dict_entries(self.entries.type_code, ctypes.byref(view), self.n_entries, t.data_ptr(),
+                                              dev.index or 0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            Dictionary.entries_calls += 1
+            self._table = t
+        return self._table
+
+    def decode(self, col: Column) -> Column:
+        """The plain utf8 / large_utf8 Column a dict_utf8 column of this dictionary stands for (dq_dict_decode)."""
+        return self.decode_buffers(col.name, col.n_rows, col.values.data_ptr(),
+                                   col.validity.data_ptr() if col.validity is not None else None)
+
+    def decode_buffers(self, name: str, n: int, indices_ptr: int, validity_ptr: Optional[int]) -> Column:
+        """decode() of int32 indices / validity given as device addresses (an uploaded Arrow batch's slot)."""
+        import ctypes
+
+        torch = _torch()
+        dev = self.entries.values.device
+        large = self.entries.dtype == "large_utf8"
+        ow = 8 if large else 4
+        offsets = torch.zeros(((n + 1) * ow + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
+        validity = torch.zeros(((n + 63) // 64) * 8 + 8, dtype=torch.uint8, device=dev)
+        dview = self.entries.view()
+        iview = L.ColumnView()
+        iview.values = indices_ptr
+        iview.validity = validity_ptr
+        need = ctypes.c_int64(0)
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            args = (self.entries.type_code, ctypes.byref(dview), self.n_entries, ctypes.byref(iview), n)
+            L.check(L.lib.dq_dict_decode(*args, None, 0, validity.data_ptr(), offsets.data_ptr(), ctypes.byref(need),
+                                         dev.index or 0, stream))
+            values = torch.zeros((need.value + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
+            if n:
+                L.check(L.lib.dq_dict_decode(*args, values.data_ptr(), need.value, validity.data_ptr(),
+                                             offsets.data_ptr(), ctypes.byref(need), dev.index or 0, stream))
+        return Column(name, self.entries.dtype, n, values, validity, offsets, nullable=True, data_bytes=need.value)
+
+
+def decoded(col: Column) -> Column:
+    """A dict_utf8 column as the plain string column it stands for (built once per column, then kept); any other
+    column unchanged."""
+    if col.dtype != "dict_utf8":
+        return col
+    if getattr(col, "_decoded", None) is None:
+        col._decoded = col.dictionary.decode(col)
+    return col._decoded
+
+
+def plain_utf8(data, columns: Optional[Iterable[str]] = None):
+    """`data` (a Table or a list of chunk Tables) with its dict_utf8 columns -- all, or those named -- replaced by
+    their decoded plain string columns: what the consumers that read string bytes (predicates, patterns, grouping,
+    histograms, schema validation, casts, row takes) ask for.  Data without such a column comes back as it is."""
+    names = None if columns is None else set(columns)
+
+    def one(t: "Table") -> "Table":
+        hit = [c.name for c in t.columns.values() if c.dtype == "dict_utf8" and (names is None or c.name in names)]
+        if not hit:
+            return t
+        return Table([decoded(c) if c.name in hit else c for c in t.columns.values()])
+
+    return one(data) if isinstance(data, Table) else [one(t) for t in data]
 
 
 class Table:
@@ -125,9 +220,15 @@ class Table:
         """{"att1": ("i32", [1, None, 3]), "name": ("utf8", ["a", None])} -> device Table."""
         cols = []
         for name, (dtype, vals) in data.items():
+            nl = True if nullable is None else nullable.get(name, True)
+            if dtype == "dict_utf8":
+                # (indices, entries) as given -- entries may be unused, repeated or None, an index None for a NULL
+                # row -- or a list of values, encoded in first-occurrence order
+                indices, entries = vals if isinstance(vals, tuple) else encode_dictionary(vals)
+                cols.append(dict_utf8_column(name, list(indices), list(entries), device=device, nullable=nl))
+                continue
             vals = list(vals)
             valid = np.array([v is not None for v in vals], dtype=bool)
-            nl = True if nullable is None else nullable.get(name, True)
             if dtype == "bool":
                 arr = np.array([False if v is None else bool(v) for v in vals], dtype=bool)
                 cols.append(column_from_numpy(name, dtype, arr, valid, device=device, nullable=nl))
@@ -192,3 +293,39 @@ def utf8_column(name: str, values: Sequence[Optional[bytes]], device: str = "cud
     return Column(name, "large_utf8" if large else "utf8", n, torch.from_numpy(raw).to(device),
                   torch.from_numpy(pack_validity(valid)).to(device) if nullable else None, ot,
                   nullable=nullable, data_bytes=int(offs[-1]))
+
+
+def encode_dictionary(values: Iterable) -> Tuple[List[Optional[int]], List]:
+    """(indices, entries) of a list of values: the distinct non-None values in first-occurrence order, None rows
+    as None indices (no NULL entry)."""
+    entries, seen, indices = [], {}, []
+    for v in values:
+        if v is not None and v not in seen:
+            seen[v] = len(entries)
+            entries.append(v)
+        indices.append(None if v is None else seen[v])
+    return indices, entries
+
+
+def _as_bytes(v):
+    return None if v is None else (v.encode("utf-8") if isinstance(v, str) else bytes(v))
+
+
+def dict_utf8_column(name: str, indices: Sequence[Optional[int]], dictionary_values, valid: Optional[np.ndarray] = None,
+                     device: str = "cuda", nullable: bool = True, large: bool = False) -> Column:
+    """A dictionary-encoded string column: int32 `indices` (None: a NULL row) into `dictionary_values` -- a sequence
+    of str / bytes / None entries, or a Dictionary shared with other columns and chunks.  Indices of non-NULL rows
+    must lie in [0, number of entries) (ValueError otherwise: the device never sees an unchecked index)."""
+    d = dictionary_values if isinstance(dictionary_values, Dictionary) else Dictionary(
+        utf8_column(name, [_as_bytes(v) for v in dictionary_values], device=device, large=large))
+    ok = np.array([i is not None for i in indices], dtype=bool)
+    if valid is not None:
+        ok &= np.asarray(valid, dtype=bool)
+    idx = np.array([0 if i is None else int(i) for i in indices], dtype=np.int64)
+    bad = ok & ((idx < 0) | (idx >= d.n_entries))
+    if bad.any():
+        r = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"dictionary index {int(idx[r])} at row {r} is outside the dictionary's {d.n_entries} entries")
+    idx[~ok] = 0
+    c = column_from_numpy(name, "i32", idx.astype(np.int32), ok, device=device, nullable=nullable)
+    return Column(name, "dict_utf8", c.n_rows, c.values, c.validity, None, nullable=c.nullable, dictionary=d)

@@ -75,10 +75,17 @@ enum dq_type {
   DQ_TYPE_BOOL = 9,       /* BooleanType: LSB-first bit-packed values (Arrow `b`), bit 0 = row 0 of the chunk */
   DQ_TYPE_DATE32 = 10,    /* DateType: int32 days since 1970-01-01 (Arrow `tdD`) */
   DQ_TYPE_TIMESTAMP = 11, /* TimestampType: int64 microseconds since the epoch (Arrow `tsu:<timezone>`) */
-  DQ_TYPE_DECIMAL128 = 12 /* DecimalType(p, s): 16-byte little-endian two's-complement unscaled values (Arrow
+  DQ_TYPE_DECIMAL128 = 12,/* DecimalType(p, s): 16-byte little-endian two's-complement unscaled values (Arrow
                              `d:p,s` / `d:p,s,128`); use the code DQ_DECIMAL128(p, s) */
+  DQ_TYPE_DICT_UTF8 = 13  /* StringType carried as int32 indices into a dictionary of strings (Arrow dictionary
+                             arrays).  The dictionary's bytes never reach dq_scan: a view passes the indices in
+                             `values`, their bitmap in `validity`, the dictionary's entry words (dq_dict_entries,
+                             uint32 each, device) in `offsets` and the number of entries in `reserved`.  A plan
+                             takes such a column as col_a of COMPLETENESS / APPROX_COUNT_DISTINCT / DATATYPE (with
+                             or without a `where` over other columns); any other use is DQ_E_UNSUPPORTED: decode
+                             it (dq_dict_decode) and pass the UTF8 column */
 };
-#define DQ_TYPE_MAX 12
+#define DQ_TYPE_MAX 13
 #define DQ_DECIMAL128(p, s) (DQ_TYPE_DECIMAL128 | ((p) << 8) | ((s) << 16))
 #define DQ_TYPE_BASE(t) ((t) & 0xFF)
 #define DQ_DECIMAL_PRECISION(t) (((t) >> 8) & 0xFF)
@@ -165,8 +172,39 @@ typedef struct dq_column_view {
   const void* values;
   const uint8_t* validity;
   const void* offsets;
-  int64_t reserved; /* must be 0 */
+  int64_t reserved; /* must be 0 (DQ_TYPE_DICT_UTF8: the number of dictionary entries) */
 } dq_column_view;
+
+/* ---- Dictionary-encoded string columns (DQ_TYPE_DICT_UTF8) ----
+ * dq_dict_entries: one pass over a dictionary's n_entries strings (dict: a DQ_TYPE_UTF8 / DQ_TYPE_LARGE_UTF8 view
+ * of them, device pointers; validity NULL = no NULL entry) that writes one uint32 entry word per entry to
+ * entries_out (device, 4-byte aligned), asynchronously on hip_stream:
+ *   bits 0..8    the entry's HLL register index: the top 9 bits of XXH64(bytes, seed 42)
+ *   bits 9..14   its rank pw (1..56) as StatefulHyperloglogPlus computes it from the same hash
+ *   bits 15..17  its StatefulDataType class: 1 FRACTIONAL, 2 INTEGRAL, 3 BOOLEAN, 4 STRING
+ *   bit 18       1 for a non-NULL entry; a NULL entry's word is 0
+ *   bits 19..31  reserved, written 0
+ * The word does not depend on a plan: compute a dictionary's table once and pass it to every plan and chunk that
+ * sees the dictionary.  In dq_scan a row of such a column is NULL iff its validity bit is 0, its entry is NULL or
+ * its index lies outside [0, reserved) (such a row's entry is never loaded; validate indices on the host --
+ * dq_dict_check_indices); entries no row refers to influence nothing, duplicate entries are harmless.
+ * dq_dict_decode: the plain string column (of dict_type) a dictionary column stands for, in the layout dq_take_rows
+ * writes: out_offsets n_rows + 1 offsets of dict's width, out_values the bytes (values_capacity = its size),
+ * out_validity (NULL: not wanted) ceil(n_rows / 64) 64-bit words.  indices: values = int32 indices, validity = their
+ * bitmap or NULL.  With out_values NULL the call writes the offsets and *data_bytes only (the sizing call).
+ * Synchronises hip_stream. */
+dq_status dq_dict_entries(int32_t dict_type, const dq_column_view* dict, int64_t n_entries, uint32_t* entries_out,
+                          int32_t device, void* hip_stream);
+dq_status dq_dict_decode(int32_t dict_type, const dq_column_view* dict, int64_t n_entries,
+                         const dq_column_view* indices, int64_t n_rows, void* out_values, int64_t values_capacity,
+                         uint8_t* out_validity, void* out_offsets, int64_t* data_bytes, int32_t device,
+                         void* hip_stream);
+/* Host: widen n indices of index_type (DQ_TYPE_I8 / I16 / I32, or the unsigned widths as -DQ_TYPE_I8 / -DQ_TYPE_I16)
+ * to int32 in out (may be NULL: check only) and check 0 <= index < n_entries for every row whose validity bit
+ * (LSB-first bitmap starting at bit validity_bit of validity[0]; NULL: every row) is set.  DQ_E_INVALID names the
+ * first offending row. */
+dq_status dq_dict_check_indices(int32_t index_type, const void* indices, int64_t n, const uint8_t* validity,
+                                int32_t validity_bit, int64_t n_entries, int32_t* out);
 
 /* ---- Host ingestion: Arrow C Data Interface batches -> device chunks (no JVM in the data path) ----
  * The Arrow C Data Interface ABI (arrow.apache.org/docs/format/CDataInterface.html), as exported by
@@ -223,6 +261,17 @@ typedef struct dq_host_column {
  * types, nested / dictionary arrays.  DQ_E_INVALID: a required buffer is NULL (an empty array may
  * export NULL buffers: it maps to an empty column). */
 dq_status dq_arrow_import(const struct ArrowSchema* schema, const struct ArrowArray* array, dq_host_column* out);
+/* A dictionary-encoded Arrow array is two columns.  *indices (index formats c, s, i, C, S; slices honoured as above):
+ * a host column of type DQ_TYPE_DICT_UTF8 whose `values` are the Arrow index bytes, `reserved` their type as
+ * dq_dict_check_indices names it (DQ_TYPE_I8 / I16 / I32, negated for the unsigned formats), `offset_base` the number
+ * of dictionary entries and value_bytes = 4 * n_rows: dq_upload widens the indices to int32 while it copies them into
+ * the pinned slot and, in that loop, checks 0 <= index < entries for every valid row -- a violation is DQ_E_INVALID
+ * naming the row, and nothing is uploaded.  The device view dq_upload returns holds the int32 indices and their
+ * validity; the caller adds the entry table (`offsets`) and the entry count (`reserved`).  *dictionary (value formats
+ * u, U; a sliced dictionary included): an ordinary UTF8 / LARGE_UTF8 host column of the entries, uploaded once per
+ * dictionary.  DQ_E_UNSUPPORTED: other index widths, other value types, a nested dictionary. */
+dq_status dq_arrow_import_dictionary(const struct ArrowSchema* schema, const struct ArrowArray* array,
+                                     dq_host_column* indices, dq_host_column* dictionary);
 /* Pinned, n-buffered host -> device upload.  dq_upload copies one chunk's columns (CPU threads: host ->
  * pinned slot; DMA on the uploader's own stream: pinned -> device slot) and returns device views of the
  * slot, valid until the slot is reused n_slots uploads later.  Before scanning, make the scan stream wait
@@ -364,7 +413,8 @@ int64_t dq_plan_bytes_per_row_x1000(const dq_plan* plan);
 int32_t dq_plan_num_launches(const dq_plan* plan);
 /* Optional per-kernel timing (hipEvents recorded on the launch stream around every launch).
  * kernel: 0 = predicate pass, 1 = all column-pass launches, 2 = pair (correlation) pass,
- * 3 = finalize, 16 + v = column-pass launches of variant v (see deequ_amd/csrc/dq_device.h).
+ * 3 = finalize, 4 = the dictionary row pass (DQ_TYPE_DICT_UTF8 columns; not part of 1),
+ * 16 + v = column-pass launches of variant v (see deequ_amd/csrc/dq_device.h).
  * dq_plan_kernel_time synchronises, then returns the summed duration and launch count since
  * timing was (re-)enabled. */
 dq_status dq_plan_enable_timing(dq_plan* plan, int32_t on);
