@@ -357,6 +357,11 @@ def _load():
     L.dq_dict_decode.restype = c.c_int32
     L.dq_dict_decode.argtypes = [c.c_int32, P(ColumnView), c.c_int64, P(ColumnView), c.c_int64, c.c_void_p, c.c_int64,
                                  c.c_void_p, c.c_void_p, P(c.c_int64), c.c_int32, c.c_void_p]
+    L.dq_dict_count.restype = c.c_int32
+    L.dq_dict_count.argtypes = [P(ColumnView), c.c_int64, c.c_void_p, c.c_int32, c.c_void_p]
+    L.dq_freq_build_weighted.restype = c.c_int32
+    L.dq_freq_build_weighted.argtypes = [P(c.c_int32), c.c_int32, P(ColumnView), P(c.c_int64), P(c.c_void_p), c.c_int32,
+                                         c.c_int32, c.c_void_p, P(c.c_void_p)]
     L.dq_dict_check_indices.restype = c.c_int32
     L.dq_dict_check_indices.argtypes = [c.c_int32, c.c_void_p, c.c_int64, c.c_void_p, c.c_int32, c.c_int64, c.c_void_p]
     L.dq_arrow_import_dictionary.restype = c.c_int32
@@ -394,6 +399,7 @@ EXPORTED = [
     "dq_schema_plan_create", "dq_schema_plan_destroy", "dq_schema_validate", "dq_schema_check_host",
     "dq_take_index", "dq_take_rows", "dq_split_rows", "dq_split_rows_host",
     "dq_dict_entries", "dq_dict_decode", "dq_dict_check_indices", "dq_arrow_import_dictionary",
+    "dq_dict_count", "dq_freq_build_weighted",
 ]
 
 

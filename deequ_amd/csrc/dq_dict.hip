@@ -7,9 +7,13 @@
 //                     privatised LDS HLL registers the utf8_* column variants fill.  No string byte is read.
 //   dq_dict_decode    (index, validity, entry non-null) -> gather index + output validity, then dq_take_rows'
 //                     string gather (dq::take_strings, dq_schema.hip): the plain UTF8 column.
+//   dq_dict_count     counts[e] += rows that carry index e (valid row, index inside the table, entry non-NULL): the
+//                     grouping of the column, from which dq_freq_build_weighted makes the frequency table.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 #include "dq_device.h"
 #include "dq_hash.h"
@@ -225,6 +229,66 @@ __global__ __launch_bounds__(kBlock) void dq_dict_gather_index(const int32_t* __
   if (lane == 0 && g * 64 < n_rows && out_validity) out_validity[g] = m;
 }
 
+// ------------------------------------------------------------------------------------------
+// Index count
+// ------------------------------------------------------------------------------------------
+// A table of at most this many entries is counted in a workgroup-private LDS table of uint32 counters (16 KB: eight
+// workgroups, the CU's 32 waves, hold 128 KB of its 160 KB; twice as many entries would leave room for five)
+constexpr int32_t kDictCountLdsEntries = 4096;
+constexpr int32_t kDictCountMaxWG = 2048;  // row ranges per launch: eight workgroups per CU
+
+// Workgroup b counts rows [b rows_per_range, (b + 1) rows_per_range), lane l of a wave taking row base + 64 j + l as
+// dq_dict_scan does (rows_per_range is a multiple of kRowsPerIter: a 64-row group's validity is one scalar word).  A
+// row counts when its validity bit is set, (uint32_t)idx < D and its entry word has the non-NULL bit -- dq_dict_scan's
+// rule for a non-NULL row; an index that fails the compare touches neither table.
+// STAGED: the counters live in LDS (a range is below 2^31 rows: they cannot wrap) and are added to counts[] once per
+// workgroup, entry e by lane e % 256 (consecutive 8-byte adds), where the entry's non-NULL bit is looked at -- once
+// per entry and workgroup, not per row.  Not STAGED: one global add per counted row.  (Combining the equal indices
+// of a 64-row group before the LDS add -- one pass per distinct index -- was measured and lost)
+template <bool STAGED>
+__global__ __launch_bounds__(kBlock) void dq_dict_count_kernel(const int32_t* __restrict__ indices,
+                                                               const uint32_t* validity,
+                                                               const uint32_t* __restrict__ gtab, uint32_t D,
+                                                               int64_t n_rows, int64_t rows_per_range,
+                                                               unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t cnt[STAGED ? kDictCountLdsEntries : 1];
+  const int64_t row0 = (int64_t)blockIdx.x * rows_per_range;
+  int64_t row1 = row0 + rows_per_range;
+  if (row1 > n_rows) row1 = n_rows;
+  if constexpr (STAGED) {
+    for (uint32_t i = threadIdx.x; i < D; i += kBlock) cnt[i] = 0;
+    __syncthreads();
+  }
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int32_t nr = (int32_t)(row1 - row0);
+  for (int32_t rb = wave * 512; rb < nr; rb += kRowsPerIter) {
+#pragma unroll 2
+    for (int j = 0; j < 8; ++j) {
+      const int32_t left = nr - rb - 64 * j;  // rows of this group below row1
+      if (left <= 0) break;
+      const int64_t gbase = row0 + rb + 64 * j;
+      const uint64_t m = sel_word(validity, gbase >> 5, left);
+      if (m == 0) continue;
+      uint32_t idx = D;
+      if (lane_bit(m)) idx = (uint32_t)indices[gbase + lane];
+      const bool in = idx < D;
+      if constexpr (STAGED) {
+        if (in) atomicAdd(&cnt[idx], 1u);
+      } else {
+        if (in && (gtab[idx] & kDictNonNull)) atomicAdd(&counts[idx], 1ull);
+      }
+    }
+  }
+  if constexpr (STAGED) {
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < D; e += kBlock) {
+      const uint32_t c = cnt[e];
+      if (c && (gtab[e] & kDictNonNull)) atomicAdd(&counts[e], (unsigned long long)c);
+    }
+  }
+}
+
 }  // namespace dq
 
 extern "C" {
@@ -287,6 +351,41 @@ dq_status dq_dict_decode(int32_t dict_type, const dq_column_view* dict, int64_t 
   // (take_strings synchronises the stream before it returns: the gather index is freed after its last use)
   return take_strings(dict_type == DQ_TYPE_LARGE_UTF8, dict, n_entries, gather.get(), n_rows, out_values,
                       values_capacity, out_offsets, data_bytes, st, me);
+}
+
+dq_status dq_dict_count(const dq_column_view* indices, int64_t n_rows, int64_t* counts, int32_t device,
+                        void* hip_stream) {
+  using namespace dq;
+  const char* me = "dq_dict_count";
+  if (!indices || indices->reserved < 0 || indices->reserved > INT32_MAX || n_rows < 0)
+    return set_error(DQ_E_INVALID, "%s: bad argument", me);
+  if (n_rows > INT32_MAX) return set_error(DQ_E_UNSUPPORTED, "%s: at most 2^31 - 1 rows per call", me);
+  const uint32_t D = (uint32_t)indices->reserved;
+  if (n_rows == 0 || D == 0) return DQ_OK;  // (no entry: every row is NULL)
+  if (!indices->values || !indices->offsets || !counts) return set_error(DQ_E_INVALID, "%s: NULL buffer", me);
+  if (((uintptr_t)indices->values & 3) || ((uintptr_t)indices->validity & 3) || ((uintptr_t)indices->offsets & 3) ||
+      ((uintptr_t)counts & 7))
+    return set_error(DQ_E_INVALID, "%s: misaligned buffer", me);
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  DQ_HIP(hipSetDevice(device));
+  // row ranges: whole kRowsPerIter blocks, at most kDictCountMaxWG of them
+  const int64_t blocks = (n_rows + kRowsPerIter - 1) / kRowsPerIter;
+  const int64_t rows_per_range = (blocks + kDictCountMaxWG - 1) / kDictCountMaxWG * kRowsPerIter;
+  const unsigned grid = (unsigned)((n_rows + rows_per_range - 1) / rows_per_range);
+  // DQ_DICT_COUNT_AB=global (dqscan.h; A/B runs of tools/dict_bench.py): a small table is counted with global adds
+  // too; exactly that value, read per call
+  const char* knob = std::getenv("DQ_DICT_COUNT_AB");
+  const bool staged = D <= (uint32_t)kDictCountLdsEntries && !(knob && std::strcmp(knob, "global") == 0);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, static_cast<const int32_t*>(indices->values),
+                       reinterpret_cast<const uint32_t*>(indices->validity),
+                       static_cast<const uint32_t*>(indices->offsets), D, n_rows, rows_per_range,
+                       reinterpret_cast<unsigned long long*>(counts));
+  };
+  if (staged) launch(dq_dict_count_kernel<true>);
+  else launch(dq_dict_count_kernel<false>);
+  DQ_HIP(hipGetLastError());
+  return DQ_OK;
 }
 
 }  // extern "C"

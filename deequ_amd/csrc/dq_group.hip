@@ -47,11 +47,13 @@ struct GroupCols {
   int32_t type[kMaxGroupCols];
   int32_t n_cols;
   uint64_t key_mask;  // applied to the primary tuple hash: ~0, or fewer bits from DQ_TEST_GROUP_HASH_MASK (tests)
+  const int64_t* weight;  // dq_freq_build_weighted: row r stands for weight[r] rows (<= 0: for none); else NULL
 };
 
 constexpr uint64_t kSeed2 = 0x9E3779B97F4A7C15ull;  // seed of the second (verification) tuple hash
 
 __device__ __forceinline__ bool row_valid(const GroupCols& g, int64_t r) {
+  if (g.weight && g.weight[r] <= 0) return false;
   for (int c = 0; c < g.n_cols; ++c)
     if (g.validity[c] && !((g.validity[c][r >> 5] >> (r & 31)) & 1u)) return false;
   return true;
@@ -515,6 +517,26 @@ __global__ void gather_rep(const uint64_t* __restrict__ sorted_rows, const int64
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x)
     rep[g] = sorted_rows[starts[g]];
 }
+// a weighted table (dq_freq_build_weighted): counts[g], on entry the length of group g's run of the sorted row ids,
+// becomes the sum of those rows' weights; *total += every group's (one thread per group: a run is the entries that
+// share a value, a few)
+__global__ void weighted_counts(const uint64_t* __restrict__ sorted_rows, const int64_t* __restrict__ starts, int64_t G,
+                                const GroupCols* __restrict__ chunks, int64_t* __restrict__ counts,
+                                unsigned long long* __restrict__ total) {
+  int64_t mine = 0;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = starts[g], n = counts[g];
+    int64_t sum = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const uint64_t r = sorted_rows[s + i];
+      sum += chunks[r >> kRowBits].weight[r & ((1ull << kRowBits) - 1)];
+    }
+    counts[g] = sum;
+    mine += sum;
+  }
+  for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(total, (unsigned long long)mine);
+}
 // The dictionary form of a low-cardinality table (dict_table): the keys of an evenly spaced sample of the compacted
 // keys (with their row ids), then every compacted key counted against the sample's distinct keys.
 __global__ void dict_sample(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ rows, int64_t n, int m,
@@ -815,8 +837,10 @@ __global__ void find_groups(const uint64_t* __restrict__ want, int32_t n, const 
 }  // namespace
 }  // namespace dq
 
+// weighted_chunks (with sorted_rows): the counts are sums of weights, added up into *d_total (zeroed by the caller)
 static dq_status rle_into(Frame& fr, dq_freq_table* t, const uint64_t* sorted, int64_t n,
-                          const uint64_t* sorted_rows = nullptr) {
+                          const uint64_t* sorted_rows = nullptr, const GroupCols* weighted_chunks = nullptr,
+                          unsigned long long* d_total = nullptr) {
   int64_t *nruns = nullptr, *starts = nullptr;
   void* tmp = nullptr;
   if (dq_status s = take(fr, nruns, 1)) return s;
@@ -832,6 +856,11 @@ static dq_status rle_into(Frame& fr, dq_freq_table* t, const uint64_t* sorted, i
     hipLaunchKernelGGL(gather_rep, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, sorted_rows, starts,
                        t->n_groups, t->d_rep.get());
     DQ_HIP(hipGetLastError());
+    if (weighted_chunks) {
+      hipLaunchKernelGGL(weighted_counts, dim3(grid_for(t->n_groups)), dim3(256), 0, t->stream, sorted_rows, starts,
+                         t->n_groups, weighted_chunks, t->d_counts.get(), d_total);
+      DQ_HIP(hipGetLastError());
+    }
     DQ_HIP(hipStreamSynchronize(t->stream));
   }
   return DQ_OK;
@@ -999,13 +1028,16 @@ static dq_status mi_from_joint(Frame& fr, dq_freq_table* t, const uint64_t* sort
 
 static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_column_view* cols,
                                  const int64_t* chunk_rows, int32_t n_chunks, int32_t device, void* hip_stream,
-                                 dq_freq_table** out, const MiRequest* mi) {
+                                 dq_freq_table** out, const MiRequest* mi, const int64_t* const* weights = nullptr) {
   if (!out) return set_error(DQ_E_INVALID, "dq_freq_build: out is NULL");
   *out = nullptr;
   if (n_cols < 1 || n_cols > kMaxGroupCols || !types)
     return set_error(DQ_E_INVALID, "dq_freq_build: 1..%d grouping columns", kMaxGroupCols);
   if (n_chunks < 0 || n_chunks > kMaxGroupChunks || (n_chunks > 0 && (!cols || !chunk_rows)))
     return set_error(DQ_E_INVALID, "dq_freq_build: bad chunks (at most %d)", kMaxGroupChunks);
+  for (int k = 0; weights && k < n_chunks; ++k)
+    if (chunk_rows[k] > 0 && (!weights[k] || ((uintptr_t)weights[k] & 7)))
+      return set_error(DQ_E_INVALID, "dq_freq_build_weighted: chunk %d has no (or misaligned) weights", k);
   for (int c = 0; c < n_cols; ++c) {
     if (!type_valid(types[c]))
       return set_error(DQ_E_TYPE, "dq_freq_build: column %d has unknown type %d", c, types[c]);
@@ -1025,11 +1057,16 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
   // one fixed-width column: grouped by its exact value bits (strings and tuples: by hash, checked exactly)
   const bool numeric1 = n_cols == 1 && types[0] != DQ_TYPE_UTF8 && types[0] != DQ_TYPE_LARGE_UTF8 && !is_decimal(types[0]);
   t->hashed = numeric1 && !mi ? 0 : 1;
+  if (weights && !t->hashed)
+    return set_error(DQ_E_UNSUPPORTED, "dq_freq_build_weighted: a single fixed-width column is its own key");
 
   // test hook: keep only some bits of the primary tuple hash, to force collisions between distinct tuples
   const uint64_t key_mask = test_hash_mask();
   std::vector<GroupCols> gcs(std::max(1, n_chunks));
-  for (int k = 0; k < n_chunks; ++k) gcs[k] = view_cols(types, n_cols, cols + (size_t)k * n_cols, key_mask, true);
+  for (int k = 0; k < n_chunks; ++k) {
+    gcs[k] = view_cols(types, n_cols, cols + (size_t)k * n_cols, key_mask, true);
+    if (weights) gcs[k].weight = weights[k];
+  }
   Frame fr(g_arena, device);
   const hipStream_t S = t->stream;
   uint64_t *sel_keys = nullptr, *sel_rows = nullptr, *sorted_keys = nullptr, *sorted_rows = nullptr;
@@ -1067,7 +1104,7 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
   }
   static const char* force = std::getenv("DQ_GROUP_VERIFY");  // A/B knob: "sorted" / "compacted"
   bool dict = false;  // low cardinality: the dictionary form (no sort; the check in compaction order)
-  if (!mi && nv > 0 && !(force && force[0] == 's'))
+  if (!mi && !weights && nv > 0 && !(force && force[0] == 's'))  // (its counts are numbers of rows)
     if (dq_status s = dict_table(fr, t, sel_keys, sel_rows, nv, end_bit, &dict)) return s;
   if (dq_status s = take(fr, sorted_keys, std::max<int64_t>(1, nv))) return s;
   if (nv > 0 && !dict) {
@@ -1087,8 +1124,15 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
     }
   }
   if (mi) return mi_from_joint(fr, t, sorted_keys, sorted_rows, nv, d_chunks, *mi);
-  if (!dict)
+  if (weights && nv > 0) {  // groups' counts and num_values: sums of weights
+    unsigned long long* d_total = nullptr;
+    if (dq_status s = take(fr, d_total, 1)) return s;
+    DQ_HIP(hipMemsetAsync(d_total, 0, 8, S));
+    if (dq_status s = rle_into(fr, t, sorted_keys, nv, sorted_rows, d_chunks, d_total)) return s;
+    if (dq_status s = read_back(&t->n_values, d_total, S)) return s;
+  } else if (!dict) {
     if (dq_status s = rle_into(fr, t, sorted_keys, nv, t->hashed ? sorted_rows : nullptr)) return s;
+  }
   if (t->hashed && nv > 0) {
     // few groups (rows repeat their group's tuple many times): each row checked against its group's representative
     // in compaction order; otherwise equal-hash neighbours in sorted order (which the dictionary form has not made)
@@ -1192,6 +1236,13 @@ static dq_status mi_from_joint(Frame& fr, dq_freq_table* t, const uint64_t* sort
 dq_status dq_freq_build(const int32_t* types, int32_t n_cols, const dq_column_view* cols, const int64_t* chunk_rows,
                         int32_t n_chunks, int32_t device, void* hip_stream, dq_freq_table** out) {
   return freq_build_impl(types, n_cols, cols, chunk_rows, n_chunks, device, hip_stream, out, nullptr);
+}
+
+dq_status dq_freq_build_weighted(const int32_t* types, int32_t n_cols, const dq_column_view* cols,
+                                 const int64_t* chunk_rows, const int64_t* const* weights, int32_t n_chunks,
+                                 int32_t device, void* hip_stream, dq_freq_table** out) {
+  if (n_chunks > 0 && !weights) return set_error(DQ_E_INVALID, "dq_freq_build_weighted: weights is NULL");
+  return freq_build_impl(types, n_cols, cols, chunk_rows, n_chunks, device, hip_stream, out, nullptr, weights);
 }
 
 dq_status dq_mutual_information(const int32_t* types, const dq_column_view* cols, const int64_t* chunk_rows,

@@ -191,16 +191,68 @@ def _views(chunks, columns: Sequence[str]):
     return views, rows
 
 
-def build_frequencies(data, columns: Sequence[str]) -> "FrequenciesAndNumRows":
-    """computeFrequencies(data, columns) + numRows = data.count() on the GPU."""
-    from .table import plain_utf8
+def index_path_dictionaries(chunks, columns: Sequence[str]):
+    """The distinct Dictionary objects of a grouping that is computed on dictionary indices, else None.  The index
+    path takes a grouping over exactly one column that is dict_utf8 in every chunk, when the distinct dictionaries
+    together hold no more entries than the chunks hold rows (beyond that the entries are more work than the rows).
+    Everything else -- tuples of columns, a mix of plain and dictionary chunks -- reads the decoded column."""
+    if len(columns) != 1 or not chunks:
+        return None
+    cols = [t.columns.get(columns[0]) for t in chunks]
+    if any(c is None or c.dtype != "dict_utf8" for c in cols):
+        return None
+    dicts = list({id(c.dictionary): c.dictionary for c in cols}.values())
+    if len({d.entries.dtype for d in dicts}) != 1:  # (one table type: utf8 or large_utf8 entries throughout)
+        return None
+    if sum(d.n_entries for d in dicts) > sum(t.num_rows for t in chunks):
+        return None
+    return dicts
 
-    data = plain_utf8(data)  # (dictionary-encoded string columns: read as the plain columns they stand for)
+
+def _frequencies_from_indices(chunks, column: str, dicts) -> "FrequenciesAndNumRows":
+    """The frequency table of a dictionary column without its strings' bytes per row: the rows of every chunk counted
+    per entry (dq_dict_count, one int64 array per distinct dictionary), then dq_freq_build_weighted over the
+    dictionaries' entries -- one input chunk per dictionary -- with those counts as weights.  Entries no row carries
+    and NULL entries make no group, entries of equal bytes (in one dictionary or in two) make one.  The state's
+    representative rows point into the entries, which are its source tables."""
+    import dataclasses
+
     import torch
 
+    from .table import Table
+
+    dev = torch.cuda.current_device()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    counts = {id(d): torch.zeros(max(1, d.n_entries), dtype=torch.int64, device=d.entries.values.device) for d in dicts}
+    for t in chunks:
+        col = t.columns[column]
+        view = col.view()
+        L.check(L.lib.dq_dict_count(ctypes.byref(view), t.num_rows, counts[id(col.dictionary)].data_ptr(), dev, stream))
+    entry_chunks = [Table([dataclasses.replace(d.entries, name=column)]) for d in dicts]
+    types = (ctypes.c_int32 * 1)(_gpu_type(dicts[0].entries.dtype))
+    views, rows = _views(entry_chunks, [column])
+    weights = (ctypes.c_void_p * len(dicts))(*[counts[id(d)].data_ptr() for d in dicts])
+    h = ctypes.c_void_p()
+    L.check(L.lib.dq_freq_build_weighted(types, 1, views, rows, weights, len(dicts), dev, stream, ctypes.byref(h)))
+    return FrequenciesAndNumRows(FreqTable(h, list(types)), sum(t.num_rows for t in chunks),
+                                 source=(entry_chunks, [column]))
+
+
+def build_frequencies(data, columns: Sequence[str]) -> "FrequenciesAndNumRows":
+    """computeFrequencies(data, columns) + numRows = data.count() on the GPU.  A single dictionary-encoded column is
+    grouped on its indices (index_path_dictionaries); the table is the one its decoded column gives."""
     from .runner import _chunks
+    from .table import plain_utf8
 
     chunks = _chunks(data)
+    dicts = index_path_dictionaries(chunks, columns)
+    if dicts is not None:
+        return _frequencies_from_indices(chunks, columns[0], dicts)
+    # a dictionary-encoded column among the grouping's own columns is read as the plain column it stands for; the
+    # table's other dictionary columns are not touched
+    chunks = plain_utf8(chunks, columns)
+    import torch
+
     schema = {name: dt for name, dt, _ in chunks[0].schema}
     types = (ctypes.c_int32 * len(columns))(*[_gpu_type(schema[c]) for c in columns])
     views, rows = _views(chunks, columns)
@@ -577,9 +629,6 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
                 from .metrics import UnsupportedOnGpuPathException
 
                 raise UnsupportedOnGpuPathException(f"{self}: a binning UDF runs in Spark, not on the GPU path")
-            from .table import plain_utf8
-
-            data = plain_utf8(data, [self.column])  # (the bins' values are rendered from the plain column)
             state = build_frequencies(data, [self.column])
             if aggregateWith is not None or saveStatesWith is not None:
                 state.materialize()  # once, before the merge and the first persist
@@ -589,6 +638,8 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
                     state = state.sum(prev)
             if saveStatesWith is not None:
                 saveStatesWith.persist(self, state)
-            return self.computeMetricFromState(state, data)
+            # the bins' values are rendered from the tables the state's representative rows point into: the chunks (a
+            # dictionary column read as bytes: its decoded twin), or the entries of a column grouped on its indices
+            return self.computeMetricFromState(state, state._source[0] if state._source is not None else data)
         except Exception as e:
             return self.toFailureMetric(e)

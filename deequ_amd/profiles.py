@@ -199,11 +199,34 @@ def _distribution(counts: Dict[str, int], nulls: int) -> Distribution:
     return Distribution({k: DistributionValue(c, c / total) for k, c in counts.items()}, numberOfBins=len(counts))
 
 
-def _fallback_distribution(data, column: str) -> Distribution:
-    """A column over the fused pass's capacity, through the grouping path: every group of build_frequencies."""
-    from .grouping import Histogram, build_frequencies
+def _indices_distribution(data, column: str) -> Distribution:
+    """A dictionary column counted on its indices (grouping.index_path_dictionaries): its table from the entry
+    counts, under the fused pass's capacity rule applied to the table's groups -- the distinct non-NULL values some
+    row carries.  At most dq_cat_hist_capacity() of them: the counts from one export and the values from one
+    dq_freq_take_values call over the materialised table (the entries the groups stand for), as the fused pass exports
+    a plain column.  More: the fallback of a plain column over capacity, on the same table."""
+    from .grouping import build_frequencies
 
     state = build_frequencies(data, [column])
+    if int(L.lib.dq_freq_num_groups(state.frequencies.handle)) > int(L.lib.dq_cat_hist_capacity()):
+        return _fallback_distribution(data, column, state)
+    nulls = state.numRows - state.frequencies.summary(state.numRows).num_values
+    keys, cnts = state.frequencies.export()
+    if len(keys) == 0:
+        return _distribution({}, nulls)
+    values = state.materialize().frequencies.take_values(keys, 0)
+    return _distribution({v.decode("utf-8", "replace"): int(c) for v, c in zip(values, cnts)}, nulls)
+
+
+def _fallback_distribution(data, column: str, state=None) -> Distribution:
+    """A column over the fused pass's capacity, through the grouping path: every group of build_frequencies (or of
+    `state`, that call's result)."""
+    from .grouping import Histogram, build_frequencies
+
+    if state is None:
+        state = build_frequencies(data, [column])
+    if state._source is not None:  # (the tables the representative rows point into: see Histogram.calculate)
+        data = state._source[0]
     n = int(L.lib.dq_freq_num_groups(state.frequencies.handle))
     keys = (ctypes.c_uint64 * max(1, n))()
     cnts = (ctypes.c_int64 * max(1, n))()
@@ -260,14 +283,21 @@ def build_cat_hist(data, columns: Sequence[str]):
 def compute_histograms(data, columns: Sequence[str]) -> Dict[str, Distribution]:
     """computeHistograms (:518-565) on the device: the Distribution of every target column from one fused pass (at
     most MAX_COLUMNS_PER_CALL columns per call); a column over the pass's capacity goes through build_frequencies and
-    gives the same Distribution."""
+    gives the same Distribution.  A dictionary-encoded column that build_frequencies groups on its indices
+    (grouping.index_path_dictionaries) gets its Distribution from the entry counts (_indices_distribution: the same
+    capacity rule over its distinct values, the same fallback), its strings are not decoded; any other dictionary
+    column is read as the plain column it stands for."""
+    from .grouping import index_path_dictionaries
     from .table import plain_utf8
 
-    data = plain_utf8(data)  # (dictionary-encoded string columns: read as the plain columns they stand for)
-    columns = list(columns)
+    requested = list(columns)
+    chunks = _chunks(data)
+    on_indices = [c for c in requested if index_path_dictionaries(chunks, [c]) is not None]
+    columns = [c for c in requested if c not in on_indices]
+    data = plain_utf8(chunks, columns)
     chunks = _chunks(data)
     schema = {name: dt for name, dt, _ in chunks[0].schema} if chunks else {}
-    out: Dict[str, Distribution] = {}
+    out: Dict[str, Distribution] = {c: _indices_distribution(data, c) for c in on_indices}
     for b in range(0, len(columns), MAX_COLUMNS_PER_CALL):
         batch = columns[b:b + MAX_COLUMNS_PER_CALL]
         for name, (status, nulls, counts, reps) in zip(batch, build_cat_hist(data, batch)):
@@ -278,7 +308,7 @@ def compute_histograms(data, columns: Sequence[str]) -> Dict[str, Distribution]:
             else:
                 out[name] = _distribution({_render_string(chunks, name, int(r)): int(c) for c, r in zip(counts, reps)},
                                           nulls)
-    return out
+    return {c: out[c] for c in requested}
 
 
 def create_profiles(columns: Sequence[str], generic: GenericColumnStatistics, numeric: NumericColumnStatistics,

@@ -33,8 +33,10 @@ def _chunks(data) -> List[Table]:
 def dictionary_columns_to_decode(schema, analyzers: Sequence[Analyzer]) -> set:
     """The dict_utf8 columns of `schema` that a run of `analyzers` reads as string bytes.  A column stays encoded (the
     plan's dictionary row pass reads indices only) while the run refers to it only as the column of Completeness /
-    ApproxCountDistinct / DataType; any other reference -- a predicate or `where` atom, PatternMatch, a grouping
-    column, an analyzer with a device pass of its own -- needs the decoded plain column."""
+    ApproxCountDistinct / DataType or as the single column of a grouping (Uniqueness, Distinctness, CountDistinct,
+    UniqueValueRatio, Entropy, Histogram: grouping.build_frequencies counts its indices, or decodes it itself where
+    its rule says so); any other reference -- a predicate or `where` atom, PatternMatch, a grouping over several
+    columns, MutualInformation, an analyzer with a device pass of its own -- needs the decoded plain column."""
     from .analyzers import ApproxCountDistinct, Completeness, DataType
     from .metrics import NoSuchColumnException
 
@@ -49,7 +51,9 @@ def dictionary_columns_to_decode(schema, analyzers: Sequence[Analyzer]) -> set:
             if isinstance(a, (Completeness, ApproxCountDistinct, DataType)) and a.column in dict_cols:
                 b.pred(a.where)  # only its `where` reads other columns' values
             elif getattr(a, "grouping", False):
-                b.columns.extend(a.groupingColumns() if hasattr(a, "groupingColumns") else [a.column])
+                cols = a.groupingColumns() if hasattr(a, "groupingColumns") else [a.column]
+                if len(cols) != 1:  # (a single grouping column is left to build_frequencies)
+                    b.columns.extend(cols)
             else:
                 a._lower(b)
         except (UnsupportedPredicate, NoSuchColumnException):

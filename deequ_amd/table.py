@@ -112,6 +112,7 @@ class Dictionary:
     decoded plain column of a given index column are built on first use and kept."""
 
     entries_calls = 0  # dq_dict_entries launches of the process (tests count them)
+    decode_calls = 0   # columns decoded by the process (dq_dict_decode): a run on the indices alone adds none
 
     def __init__(self, entries: Column):
         if entries.dtype not in ("utf8", "large_utf8"):
@@ -145,6 +146,7 @@ class Dictionary:
         """decode() of int32 indices / validity given as device addresses (an uploaded Arrow batch's slot)."""
         import ctypes
 
+        Dictionary.decode_calls += 1
         torch = _torch()
         dev = self.entries.values.device
         large = self.entries.dtype == "large_utf8"
@@ -180,8 +182,9 @@ def decoded(col: Column) -> Column:
 
 def plain_utf8(data, columns: Optional[Iterable[str]] = None):
     """`data` (a Table or a list of chunk Tables) with its dict_utf8 columns -- all, or those named -- replaced by
-    their decoded plain string columns: what the consumers that read string bytes (predicates, patterns, grouping,
-    histograms, schema validation, casts, row takes) ask for.  Data without such a column comes back as it is."""
+    their decoded plain string columns: what the consumers that read string bytes (predicates, patterns, groupings
+    that are not computed on the indices, schema validation, casts, row takes) ask for.  Data without such a column
+    comes back as it is."""
     names = None if columns is None else set(columns)
 
     def one(t: "Table") -> "Table":

@@ -192,7 +192,21 @@ typedef struct dq_column_view {
  * writes: out_offsets n_rows + 1 offsets of dict's width, out_values the bytes (values_capacity = its size),
  * out_validity (NULL: not wanted) ceil(n_rows / 64) 64-bit words.  indices: values = int32 indices, validity = their
  * bitmap or NULL.  With out_values NULL the call writes the offsets and *data_bytes only (the sizing call).
- * Synchronises hip_stream. */
+ * Synchronises hip_stream.
+ * dq_dict_count: the grouping of a dictionary column from its indices alone.  indices: a DQ_TYPE_DICT_UTF8 view as
+ * dq_scan takes it (int32 indices, their bitmap or NULL, the entry words in `offsets`, the number of entries D in
+ * `reserved`); counts: int64[D] on the device, 8-byte aligned.  Adds to counts[e] the number of rows among the
+ * n_rows (< 2^31) that carry index e; a row counts when it is non-NULL by dq_scan's rule above (validity bit set,
+ * index inside [0, D), entry non-NULL) -- any other row is counted nowhere, and nothing outside counts[0, D) is
+ * written.  The call ACCUMULATES: the caller zeroes counts once, and the chunks that share a dictionary add into one
+ * array.  Asynchronous on hip_stream.  dq_freq_build_weighted over the dictionary's entries with these counts as
+ * weights is the frequency table dq_freq_build makes of the decoded column.
+ * Measurement hook, not for production: with the environment variable DQ_DICT_COUNT_AB=global (exactly that value,
+ * read on every call) a dictionary of at most 4096 entries is counted with global atomic adds, as larger ones are,
+ * instead of in LDS -- the same counts, 17x to 1500x slower.  Any other value, or no variable, changes
+ * nothing. */
+dq_status dq_dict_count(const dq_column_view* indices, int64_t n_rows, int64_t* counts, int32_t device,
+                        void* hip_stream);
 dq_status dq_dict_entries(int32_t dict_type, const dq_column_view* dict, int64_t n_entries, uint32_t* entries_out,
                           int32_t device, void* hip_stream);
 dq_status dq_dict_decode(int32_t dict_type, const dq_column_view* dict, int64_t n_entries,
@@ -469,6 +483,16 @@ typedef struct dq_freq_summary {
 } dq_freq_summary;
 dq_status dq_freq_build(const int32_t* types, int32_t n_cols, const dq_column_view* cols, const int64_t* chunk_rows,
                         int32_t n_chunks, int32_t device, void* hip_stream, dq_freq_table** out);
+/* dq_freq_build of rows that each stand for several: weights[k] is chunk k's device array of chunk_rows[k] int64
+ * weights, row r of the chunk counts weights[k][r] times, and a row whose weight is <= 0 is not part of the data (it
+ * makes no group).  Keys, group order, the exact check, the second hashes and the representative rows (ids into
+ * these chunks) are dq_freq_build's, the counts and num_values are sums of weights; the table is what dq_freq_build
+ * makes of the data with every row repeated weight times.  For the groupings keyed by a tuple hash (a string or
+ * decimal column, several columns); a single fixed-width column is DQ_E_UNSUPPORTED.  Used with dq_dict_count: the
+ * chunks are dictionaries' entries, the weights their counts. */
+dq_status dq_freq_build_weighted(const int32_t* types, int32_t n_cols, const dq_column_view* cols,
+                                 const int64_t* chunk_rows, const int64_t* const* weights, int32_t n_chunks,
+                                 int32_t device, void* hip_stream, dq_freq_table** out);
 dq_status dq_freq_merge(const dq_freq_table* a, const dq_freq_table* b, dq_freq_table** out);
 dq_status dq_freq_summarize(const dq_freq_table* t, int64_t num_rows, dq_freq_summary* out);
 int64_t dq_freq_num_groups(const dq_freq_table* t);
