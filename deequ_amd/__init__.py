@@ -15,8 +15,9 @@ from .repository import (AnalysisResult, AnalysisResultSerde, FileSystemMetricsR
                          InMemoryMetricsRepository, MetricsRepository, MetricsRepositoryMultipleResultsLoader,
                          ResultKey)
 from .analyzers import (ApproxCountDistinct, Completeness, Compliance, Correlation, DataType,  # noqa: F401
-                        DataTypeInstances, Maximum, Mean, Minimum, PatternMatch, Patterns, Size, StandardDeviation,
-                        Sum)
+                        DataTypeInstances, MaxLength, Maximum, Mean, MinLength, Minimum, PatternMatch, Patterns, Size,
+                        StandardDeviation, Sum)
+from .lengths import string_lengths  # noqa: F401
 from .grouping import (CountDistinct, Distinctness, Entropy, FrequenciesAndNumRows, Histogram,  # noqa: F401
                        MutualInformation, Uniqueness, UniqueValueRatio)
 from .metrics import (DoubleMetric, Distribution, DistributionValue, Entity, HistogramMetric,  # noqa: F401

@@ -256,6 +256,14 @@ def _load():
     L.dq_cast_utf8.restype = c.c_int32
     L.dq_cast_utf8.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_int32, c.c_void_p, c.c_void_p, c.c_int32,
                                c.c_void_p, P(c.c_int64)]
+    L.dq_utf8_length.restype = c.c_int32
+    L.dq_utf8_length.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p,
+                                 P(c.c_int64)]
+    L.dq_utf8_length_host.restype = c.c_int32
+    L.dq_utf8_length_host.argtypes = [c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
+    L.dq_dict_take_i32.restype = c.c_int32
+    L.dq_dict_take_i32.argtypes = [P(ColumnView), c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int32,
+                                   c.c_void_p]
     L.dq_schema_plan_create.restype = c.c_int32
     L.dq_schema_plan_create.argtypes = [P(SchemaColumn), c.c_int32, P(c.c_void_p)]
     L.dq_schema_plan_destroy.restype = None
@@ -400,6 +408,7 @@ EXPORTED = [
     "dq_take_index", "dq_take_rows", "dq_split_rows", "dq_split_rows_host",
     "dq_dict_entries", "dq_dict_decode", "dq_dict_check_indices", "dq_arrow_import_dictionary",
     "dq_dict_count", "dq_freq_build_weighted",
+    "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
 ]
 
 

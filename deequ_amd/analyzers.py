@@ -19,7 +19,7 @@ from typing import Callable, List, Optional, Sequence
 
 from . import _lib as L
 from .metrics import (DoubleMetric, EmptyStateException, Entity, Failure, NoSuchColumnException, Success,
-                      WrongColumnTypeException, wrap_if_necessary)
+                      UnsupportedOnGpuPathException, WrongColumnTypeException, wrap_if_necessary)
 from .predicates import PredicatePool
 from .states import State, state_from_c
 from .table import decimal_ps, is_numeric
@@ -59,6 +59,15 @@ class Preconditions:
         return check
 
     @staticmethod
+    def isString(column: str) -> Callable:  # (Deequ 1.0.3 Preconditions.isString)
+        def check(schema):
+            t = dict((c[0], c[1]) for c in schema)[column]
+            if spark_type(t) != "StringType":
+                raise WrongColumnTypeException(
+                    f"Expected type of column {column} to be StringType, but found {spark_type(t)} instead!")
+        return check
+
+    @staticmethod
     def findFirstFailing(schema, conditions) -> Optional[Exception]:
         for cond in conditions:
             try:
@@ -71,9 +80,11 @@ class Preconditions:
 class PlanBuilder:
     """Collects the specs, referenced columns and predicate pool of one fused plan."""
 
-    def __init__(self, table_schema):
+    def __init__(self, table_schema, length_columns: Optional[dict] = None):
         self.table_schema = list(table_schema)
         self.by_name = {c[0]: c for c in self.table_schema}
+        # source string column -> the derived length column the runner attached (lengths.attach_length_columns)
+        self.length_columns = dict(length_columns or {})
         self.columns: List[str] = []
         self.pool = PredicatePool(self)
         self.specs: List[tuple] = []
@@ -84,6 +95,16 @@ class PlanBuilder:
         if name not in self.columns:
             self.columns.append(name)
         return self.columns.index(name)
+
+    def length_col(self, name: str) -> int:
+        """The derived length column of string column `name`."""
+        if name not in self.by_name:
+            raise NoSuchColumnException(f"Input data does not include column {name}!")
+        if name not in self.length_columns:
+            raise UnsupportedOnGpuPathException(
+                f"no derived length column of {name} in this plan: MinLength / MaxLength run through AnalysisRunner "
+                "or runner.scan_states, which attach it (lengths.attach_length_columns)")
+        return self.col(self.length_columns[name])
 
     def pred(self, text: Optional[str]) -> int:
         return -1 if text is None else self.pool.add(text)
@@ -461,3 +482,7 @@ class DataType(_ColumnAnalyzer):  # DataType.scala:152-183
         from .metrics import HistogramMetric
 
         return HistogramMetric(self.column, Failure(wrap_if_necessary(e)))
+
+
+# MinLength / MaxLength (lengths.py, beside the derived column they read) belong to this module's namespace too
+from .lengths import MaxLength, MinLength, _LengthAnalyzer  # noqa: E402, F401

@@ -15,8 +15,8 @@ from __future__ import annotations
 from enum import IntEnum
 from typing import Callable, Dict, List, Optional, Sequence
 
-from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance, Correlation, Maximum, Mean, Minimum,
-                        PatternMatch, Size, StandardDeviation, Sum)
+from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance, Correlation, MaxLength, Maximum, Mean,
+                        MinLength, Minimum, PatternMatch, Size, StandardDeviation, Sum)
 from .analyzers import DataType, DataTypeInstances
 from .grouping import (Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
@@ -210,6 +210,12 @@ class Check:  # Check.scala:59-902
 
     def hasMax(self, column, assertion, hint=None):
         return self._filterable(lambda w: _named(Maximum(column, w), assertion, "MaximumConstraint", None, hint))
+
+    def hasMinLength(self, column, assertion, hint=None):  # (Deequ 1.0.3 Check.hasMinLength)
+        return self._filterable(lambda w: _named(MinLength(column, w), assertion, "MinLengthConstraint", None, hint))
+
+    def hasMaxLength(self, column, assertion, hint=None):
+        return self._filterable(lambda w: _named(MaxLength(column, w), assertion, "MaxLengthConstraint", None, hint))
 
     def hasMean(self, column, assertion, hint=None):
         return self._filterable(lambda w: _named(Mean(column, w), assertion, "MeanConstraint", None, hint))

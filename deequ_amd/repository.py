@@ -20,8 +20,8 @@ import threading
 import uuid
 from typing import Dict, Iterable, List, Optional, Sequence
 
-from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance, Correlation, DataType, Maximum, Mean,
-                        Minimum, PatternMatch, Size, StandardDeviation, Sum)
+from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance, Correlation, DataType, MaxLength, Maximum,
+                        Mean, MinLength, Minimum, PatternMatch, Size, StandardDeviation, Sum)
 from .grouping import (CountDistinct, Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
 from .metrics import (Distribution, DistributionValue, DoubleMetric, Entity, Failure, HistogramMetric,
@@ -330,7 +330,7 @@ def _gson(node, pretty: bool, serialize_nulls: bool = False, depth: int = 0) -> 
 
 _WHERE_ANALYZERS = {"Completeness": Completeness, "Sum": Sum, "Mean": Mean, "Minimum": Minimum, "Maximum": Maximum,
                     "DataType": DataType, "ApproxCountDistinct": ApproxCountDistinct,
-                    "StandardDeviation": StandardDeviation}
+                    "StandardDeviation": StandardDeviation, "MinLength": MinLength, "MaxLength": MaxLength}
 _COLUMNS_ANALYZERS = {"CountDistinct": CountDistinct, "Distinctness": Distinctness,
                       "MutualInformation": MutualInformation, "UniqueValueRatio": UniqueValueRatio,
                       "Uniqueness": Uniqueness}

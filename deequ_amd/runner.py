@@ -26,6 +26,12 @@ from .states import State
 from .table import Table, plain_utf8
 
 
+def _length_analyzers(analyzers: Sequence[Analyzer]) -> List[Analyzer]:
+    from .analyzers import _LengthAnalyzer
+
+    return [a for a in analyzers if isinstance(a, _LengthAnalyzer)]
+
+
 def _chunks(data) -> List[Table]:
     return [data] if isinstance(data, Table) else list(data)
 
@@ -36,8 +42,10 @@ def dictionary_columns_to_decode(schema, analyzers: Sequence[Analyzer]) -> set:
     ApproxCountDistinct / DataType or as the single column of a grouping (Uniqueness, Distinctness, CountDistinct,
     UniqueValueRatio, Entropy, Histogram: grouping.build_frequencies counts its indices, or decodes it itself where
     its rule says so); any other reference -- a predicate or `where` atom, PatternMatch, a grouping over several
-    columns, MutualInformation, an analyzer with a device pass of its own -- needs the decoded plain column."""
-    from .analyzers import ApproxCountDistinct, Completeness, DataType
+    columns, MutualInformation, an analyzer with a device pass of its own -- needs the decoded plain column.
+    MinLength / MaxLength read no string byte in the plan either: their derived length column is gathered from the
+    dictionary entries' lengths through the indices (lengths.string_lengths), so only their `where` counts."""
+    from .analyzers import ApproxCountDistinct, Completeness, DataType, _LengthAnalyzer
     from .metrics import NoSuchColumnException
 
     dict_cols = {c[0] for c in schema if c[1] == "dict_utf8"}
@@ -48,7 +56,8 @@ def dictionary_columns_to_decode(schema, analyzers: Sequence[Analyzer]) -> set:
     for a in analyzers:
         b = PlanBuilder(as_plain)
         try:
-            if isinstance(a, (Completeness, ApproxCountDistinct, DataType)) and a.column in dict_cols:
+            if isinstance(a, _LengthAnalyzer) or (
+                    isinstance(a, (Completeness, ApproxCountDistinct, DataType)) and a.column in dict_cols):
                 b.pred(a.where)  # only its `where` reads other columns' values
             elif getattr(a, "grouping", False):
                 cols = a.groupingColumns() if hasattr(a, "groupingColumns") else [a.column]
@@ -80,12 +89,13 @@ class ScanPlan:
     when the generator takes it, else the interpreter; "interpreter" forces the interpreter; "compiled"
     requires the compiled kernel (plan creation fails with DQError DQ_E_UNSUPPORTED instead of falling back)."""
 
-    def __init__(self, analyzers: Sequence[Analyzer], schema, device: Optional[int] = None, pred_pass: str = "auto"):
+    def __init__(self, analyzers: Sequence[Analyzer], schema, device: Optional[int] = None, pred_pass: str = "auto",
+                 length_columns: Optional[dict] = None):
         import torch
 
         self.analyzers = list(analyzers)
         self.schema = list(schema)
-        b = PlanBuilder(schema)
+        b = PlanBuilder(schema, length_columns)
         specs = (L.AnalyzerSpec * max(1, len(self.analyzers)))()
         for i, a in enumerate(self.analyzers):
             op, ca, cb, pr, wr = a._lower(b)
@@ -180,8 +190,8 @@ class ScanPlan:
             pass
 
 
-def _lower_all(analyzers: Sequence[Analyzer], schema):
-    b = PlanBuilder(schema)
+def _lower_all(analyzers: Sequence[Analyzer], schema, length_columns: Optional[dict] = None):
+    b = PlanBuilder(schema, length_columns)
     specs = (L.AnalyzerSpec * max(1, len(analyzers)))()
     for i, a in enumerate(analyzers):
         op, ca, cb, pr, wr = a._lower(b)
@@ -204,11 +214,12 @@ def _explain(b: PlanBuilder, specs, n_specs: int, pred_pass: str):
     return L.DQ_OK, buf.value.decode("utf-8", "replace")
 
 
-def explain(analyzers: Sequence[Analyzer], schema, pred_pass: str = "auto") -> str:
+def explain(analyzers: Sequence[Analyzer], schema, pred_pass: str = "auto",
+            length_columns: Optional[dict] = None) -> str:
     """The plan dq_plan_create would build for these analyzers, lowered on the host only (dq_plan_explain: no
     GPU): launches per scan, column-pass variants, the predicate program and the generated predicate kernel;
     an analyzer set over one plan's capacity is shown as the fused plans dq_plan_create splits it into."""
-    b, specs = _lower_all(analyzers, schema)
+    b, specs = _lower_all(analyzers, schema, length_columns)
     rc, text = _explain(b, specs, len(analyzers), pred_pass)
     L.check(rc)
     return text
@@ -216,8 +227,11 @@ def explain(analyzers: Sequence[Analyzer], schema, pred_pass: str = "auto") -> s
 
 def scan_results(data, analyzers: Sequence[Analyzer], pred_pass: str = "auto") -> List[L.State]:
     """Fused scan of all chunks -> raw aggregation-result slot sets, one per analyzer."""
-    chunks = _chunks(route_dictionary_columns(data, analyzers))
-    plan = ScanPlan(analyzers, chunks[0].schema, pred_pass=pred_pass)
+    from .lengths import attach_length_columns
+
+    # MinLength / MaxLength: their derived length columns, for this run only, before the dictionary routing
+    chunks = _chunks(route_dictionary_columns(attach_length_columns(data, analyzers), analyzers))
+    plan = ScanPlan(analyzers, chunks[0].schema, pred_pass=pred_pass, length_columns=chunks[0].length_columns)
     try:
         for t in chunks:
             plan.scan(t)
@@ -231,7 +245,7 @@ def scan_states(data, analyzers: Sequence[Analyzer], pred_pass: str = "auto") ->
     return {a: a._from_result(r) for a, r in zip(analyzers, res)}
 
 
-def gpu_eligible(analyzer: Analyzer, schema) -> Optional[Exception]:
+def gpu_eligible(analyzer: Analyzer, schema, length_columns: Optional[dict] = None) -> Optional[Exception]:
     """None if the analyzer lowers into a GPU plan; else the reason (-> fallback set).
 
     Two checks, both on the host: the predicate compiler (SQL text outside the GPU grammar), then the planner
@@ -239,7 +253,7 @@ def gpu_eligible(analyzer: Analyzer, schema) -> Optional[Exception]:
     limits of a plan are never a routing reason: dq_plan_create splits a set over them into several fused
     plans, so only what does not fit a plan by itself goes to the fallback."""
     try:
-        b, specs = _lower_all([analyzer], schema)
+        b, specs = _lower_all([analyzer], schema, length_columns)
     except UnsupportedPredicate as e:
         return e
     except Exception:
@@ -320,8 +334,9 @@ class AnalysisRunner:
         """doAnalysisRun from the preconditions on (AnalysisRunner.scala:137-183)."""
         if not all_analyzers:
             return AnalyzerContext.empty()
+        from .lengths import attach_length_columns, length_columns_needed
+
         schema = data_schema(data)
-        data = route_dictionary_columns(data, all_analyzers)  # (a decoded column is a StringType column too)
         passed, failures = [], {}
         for a in all_analyzers:
             err = Preconditions.findFirstFailing(schema, a.preconditions())
@@ -329,6 +344,15 @@ class AnalysisRunner:
                 passed.append(a)
             else:
                 failures[a] = a.toFailureMetric(err)
+        # the derived length columns of the MinLength / MaxLength analyzers that passed: one per source column, for
+        # this run only (new Tables; the caller's are untouched), before the dictionary routing and the plan
+        if length_columns_needed(passed):
+            try:
+                data = attach_length_columns(data, passed)
+            except Exception as e:  # the derived expression failed: its analyzers fail, the others run
+                failures.update({a: a.toFailureMetric(e) for a in _length_analyzers(passed)})
+                passed = [a for a in passed if a not in failures]
+        data = route_dictionary_columns(data, all_analyzers)  # (a decoded column is a StringType column too)
         grouping = [a for a in passed if getattr(a, "grouping", False)]
         scanning = [a for a in passed if not getattr(a, "grouping", False)]
         ctx = AnalysisRunner.runScanningAnalyzers(data, scanning, aggregateWith, saveStatesWith)
@@ -376,10 +400,13 @@ class AnalysisRunner:
                              saveStatesWith=None) -> AnalyzerContext:
         if not analyzers:
             return AnalyzerContext.empty()
+        from .lengths import length_columns_of
+
         schema = data_schema(data)
+        lengths = length_columns_of(data)
         gpu, fallback = [], {}
         for a in analyzers:
-            reason = gpu_eligible(a, schema)
+            reason = gpu_eligible(a, schema, lengths)
             if reason is None:
                 gpu.append(a)
             else:

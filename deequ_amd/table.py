@@ -191,7 +191,9 @@ def plain_utf8(data, columns: Optional[Iterable[str]] = None):
         hit = [c.name for c in t.columns.values() if c.dtype == "dict_utf8" and (names is None or c.name in names)]
         if not hit:
             return t
-        return Table([decoded(c) if c.name in hit else c for c in t.columns.values()])
+        out = Table([decoded(c) if c.name in hit else c for c in t.columns.values()])
+        out.length_columns = dict(t.length_columns)
+        return out
 
     return one(data) if isinstance(data, Table) else [one(t) for t in data]
 
@@ -209,6 +211,8 @@ class Table:
                 raise ValueError("columns differ in length")
             self.columns[c.name] = c
         self.num_rows = n or 0
+        # source string column -> its derived length column, for tables lengths.attach_length_columns built
+        self.length_columns: Dict[str, str] = {}
 
     @property
     def schema(self) -> List[Tuple[str, str, bool]]:

@@ -598,6 +598,35 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
 dq_status dq_cast_utf8(int32_t src_type, const dq_column_view* src, int64_t n_rows, int32_t to_type,
                        void* out_values, uint8_t* out_validity, int32_t device, void* hip_stream,
                        int64_t* null_count);
+/* String lengths: length(col) of a string column materialised as an I32 column, which MinLength / MaxLength read
+ * as DQ_OP_MIN / DQ_OP_MAX through dq_scan like any other column (additions under ABI 6).
+ * The length of a value is the number of its bytes b with (b & 0xC0) != 0x80.  On well-formed UTF-8 that is its
+ * number of code points, what Spark 2.2's UTF8String.numChars returns; on ill-formed bytes it is simply this rule
+ * (Spark walks lead bytes and skips by the length each announces, so the two can differ there: a lone continuation
+ * byte counts 1 for Spark and 0 here, a truncated sequence may swallow the bytes behind it for Spark).
+ * dq_utf8_length: src: a DQ_TYPE_UTF8 (int32 offsets) / DQ_TYPE_LARGE_UTF8 (int64 offsets) view of n_rows, values
+ * 16-byte aligned and readable up to the 4-byte boundary behind the last value; src->validity NULL: no NULL row.
+ * lengths: int32[n_rows]; validity_out: ceil(n_rows / 64) 64-bit words (8-byte aligned; bits past n_rows are written
+ * 0); both device, caller-allocated, and every length and every word of the n_rows rows is written.  A NULL source
+ * row gives a NULL row of length 0 whatever bytes its slot holds.  A LARGE_UTF8 value of 2^31 code points or more
+ * is stored as INT32_MAX (a UTF8 column cannot hold one).  *nulls_out (host, optional) = the NULL rows; with it the
+ * call synchronises hip_stream, without it the call is asynchronous on hip_stream.  n_rows = 0: DQ_OK, nothing
+ * written.  Another source type is DQ_E_UNSUPPORTED; a NULL or misaligned buffer, n_rows < 0, reserved != 0 are
+ * DQ_E_INVALID.
+ * dq_utf8_length_host: the same rule on the CPU, no device (tests): data, int64 offsets[n + 1], validity an LSB-first
+ * bitmap or NULL; out[r] = the length, 0 for a NULL row.
+ * dq_dict_take_i32: the per-row gather of a dictionary column: indices->values int32 indices, indices->validity
+ * their bitmap or NULL (the view's other fields are not read); out[r] = entry_values[index[r]] (device,
+ * int32[n_entries]) and row r is valid iff its index row is valid -- and, so that the call is total, its index lies
+ * inside [0, n_entries) and the entry's value is not negative (a negative value marks a NULL entry); any other row is
+ * NULL with value 0.  The index of a NULL row is neither loaded nor used to address memory.  out: int32[n_rows],
+ * validity_out: ceil(n_rows / 64) 64-bit words (8-byte aligned), every one written.  Asynchronous on hip_stream. */
+dq_status dq_utf8_length(int32_t src_type, const dq_column_view* src, int64_t n_rows, int32_t* lengths,
+                         uint64_t* validity_out, int32_t device, void* hip_stream, int64_t* nulls_out);
+dq_status dq_utf8_length_host(const uint8_t* data, const int64_t* offsets, int64_t n, const uint8_t* validity,
+                              int32_t* out);
+dq_status dq_dict_take_i32(const dq_column_view* indices, int64_t n_rows, const int32_t* entry_values,
+                           int64_t n_entries, int32_t* out, uint64_t* validity_out, int32_t device, void* hip_stream);
 /* RowLevelSchemaValidator (schema/RowLevelSchemaValidator.scala:25-282): a declared schema over string columns,
  * the per-row verdict m = toCNF(schema) (:225-281, a three-valued SQL boolean), the conforming rows cast to the
  * declared types and the other rows untouched.  One dq_schema_column per ColumnDefinition, in the schema's order:
