@@ -27,6 +27,7 @@ from .profiles import (ColumnProfiler, ColumnProfiles, NumericColumnProfile, Sta
 from .quantiles import ApproxQuantile, ApproxQuantiles  # noqa: F401
 from .runner import AnalysisRunner, AnalyzerContext, ReusingNotPossibleResultsMissingException  # noqa: F401
 from .schema import (RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator)  # noqa: F401
+from .rowlevel import (RowLevelPlan, RowLevelResults, RowOutcome, plan_row_level, row_level_results)  # noqa: F401
 from .split import random_split  # noqa: F401
 from .suggestions import (ConstraintSuggestion, ConstraintSuggestionResult, ConstraintSuggestionRunner,  # noqa: F401
                           ConstraintSuggestions, Rules, UniqueIfApproximatelyUniqueRule)

@@ -113,6 +113,11 @@ class ColumnView(ctypes.Structure):
 SCHEMA_STRING, SCHEMA_INT, SCHEMA_DECIMAL, SCHEMA_TIMESTAMP = 1, 2, 3, 4
 
 
+class RowOutput(ctypes.Structure):
+    """dq_row_output: one output of a row program (pool root of the predicate, of the `where` or -1)."""
+    _fields_ = [("pred_root", ctypes.c_int32), ("where_root", ctypes.c_int32)]
+
+
 class SchemaColumn(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("column", ctypes.c_int32), ("nullable", ctypes.c_int32),
                 ("has_min", ctypes.c_int32), ("has_max", ctypes.c_int32), ("min_value", ctypes.c_int32),
@@ -280,6 +285,21 @@ def _load():
     L.dq_take_rows.restype = c.c_int32
     L.dq_take_rows.argtypes = [c.c_int32, P(ColumnView), c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
                                c.c_void_p, c.c_void_p, P(c.c_int64), c.c_int32, c.c_void_p]
+    L.dq_row_max_outputs.restype = c.c_int32
+    L.dq_row_max_outputs.argtypes = []
+    L.dq_row_program_create.restype = c.c_int32
+    L.dq_row_program_create.argtypes = [P(ColumnDesc), c.c_int32, P(PredNode), c.c_int32, P(c.c_char_p), c.c_int32,
+                                        P(RowOutput), c.c_int32, P(c.c_void_p)]
+    L.dq_row_program_info.restype = c.c_int32
+    L.dq_row_program_info.argtypes = [c.c_void_p, P(c.c_int32), P(c.c_int32), P(c.c_int32)]
+    L.dq_row_program_destroy.restype = None
+    L.dq_row_program_destroy.argtypes = [c.c_void_p]
+    L.dq_row_outcomes.restype = c.c_int32
+    L.dq_row_outcomes.argtypes = [c.c_void_p, P(ColumnView), c.c_int64, P(c.c_void_p), P(c.c_void_p), c.c_int32,
+                                  c.c_void_p, P(c.c_int64), P(c.c_int64)]
+    L.dq_freq_unique_rows.restype = c.c_int32
+    L.dq_freq_unique_rows.argtypes = [c.c_void_p, P(c.c_int32), P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p,
+                                      c.c_void_p, P(c.c_int64), P(c.c_int64)]
     L.dq_split_rows.restype = c.c_int32
     L.dq_split_rows.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_double, c.c_void_p, c.c_void_p, c.c_int32,
                                 c.c_void_p, P(c.c_int64), P(c.c_int64)]
@@ -409,6 +429,8 @@ EXPORTED = [
     "dq_dict_entries", "dq_dict_decode", "dq_dict_check_indices", "dq_arrow_import_dictionary",
     "dq_dict_count", "dq_freq_build_weighted",
     "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
+    "dq_row_max_outputs", "dq_row_program_create", "dq_row_program_info", "dq_row_program_destroy", "dq_row_outcomes",
+    "dq_freq_unique_rows",
 ]
 
 

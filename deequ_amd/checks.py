@@ -395,6 +395,13 @@ class VerificationResult:  # VerificationResult.scala:33-36
     def successMetricsAsJson(self) -> str:
         return AnalyzerContext(self.metrics).successMetricsAsJson()
 
+    def rowLevelResults(self, data, filteredRow: str = "TRUE"):
+        """Which rows of `data` (a Table or a list of chunks) pass each check and each constraint of this run
+        (VerificationResult.rowLevelResultsAsDataFrame): rowlevel.row_level_results over the run's checks."""
+        from .rowlevel import row_level_results
+
+        return row_level_results(list(self.checkResults), data, filteredRow)
+
 
 class VerificationSuite:  # VerificationSuite.scala:42-282
     def onData(self, data) -> "VerificationRunBuilder":

@@ -834,6 +834,49 @@ __global__ void find_groups(const uint64_t* __restrict__ want, int32_t n, const 
   idx[i] = (uint64_t)lo;
   if (G == 0 || keys[lo] != k) atomicOr(missing, 1);
 }
+
+// dq_freq_unique_rows: a wave takes the 64 rows of one output word at a time.  A row whose grouping columns are all
+// non-null computes its key as group_compact does (HASHED: tuple_key, else the single column's value_bits), finds it
+// in the table's ascending keys and reads its group's count; the ballots of "count == 1" and "non-null" are the two
+// words, written by lane 0 (rows past n vote 0, so the last word's tail is 0).  The build has checked that equal keys
+// are equal tuples, so a found key is the row's group; a key the table lacks raises *missing.  tot[0] / tot[1]: the
+// set bits of the two bitmaps.
+template <bool HASHED>
+__global__ __launch_bounds__(256) void unique_rows(GroupCols g, int64_t n, const uint64_t* __restrict__ keys,
+                                                   const int64_t* __restrict__ counts, int64_t G,
+                                                   uint64_t* __restrict__ unique, uint64_t* __restrict__ grouped,
+                                                   unsigned long long* __restrict__ tot, int32_t* __restrict__ missing) {
+  const int lane = threadIdx.x & 63;
+  const int64_t words = (n + 63) >> 6;
+  unsigned long long nu = 0, ng = 0;
+  for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < words; w += (int64_t)gridDim.x * 4) {
+    const int64_t r = w * 64 + lane;
+    const bool v = r < n && row_valid(g, r);
+    bool one = false;
+    if (v) {
+      const uint64_t k = HASHED ? tuple_key(g, r) : value_bits(g, 0, r);
+      int64_t lo = 0, hi = G - 1;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < k) lo = mid + 1;
+        else hi = mid;
+      }
+      if (G == 0 || keys[lo] != k) atomicOr(missing, 1);
+      else one = counts[lo] == 1;
+    }
+    const uint64_t bu = __builtin_amdgcn_ballot_w64(one), bg = __builtin_amdgcn_ballot_w64(v);
+    if (lane == 0) {
+      unique[w] = bu;
+      if (grouped) grouped[w] = bg;
+      nu += (unsigned long long)__builtin_popcountll(bu);
+      ng += (unsigned long long)__builtin_popcountll(bg);
+    }
+  }
+  if (lane == 0 && (nu | ng)) {
+    atomicAdd(&tot[0], nu);
+    atomicAdd(&tot[1], ng);
+  }
+}
 }  // namespace
 }  // namespace dq
 
@@ -1670,6 +1713,54 @@ dq_status dq_freq_take_values(const dq_freq_table* t, const uint64_t* keys, int3
   if (values && values_cap >= got.bytes && got.bytes > 0)
     DQ_HIP(hipMemcpyAsync(values, got.values.get(), got.bytes, hipMemcpyDeviceToHost, S));
   DQ_HIP(hipStreamSynchronize(S));
+  return DQ_OK;
+}
+
+dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols, int64_t n_rows,
+                              uint64_t* unique, uint64_t* grouped, void* hip_stream, int64_t* num_unique,
+                              int64_t* num_grouped) {
+  if (!t) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: table is NULL");
+  if (n_rows < 0 || n_rows >= (1ll << 31)) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: 0 <= n_rows < 2^31");
+  if (n_rows == 0) {
+    if (num_unique) *num_unique = 0;
+    if (num_grouped) *num_grouped = 0;
+    return DQ_OK;
+  }
+  const int n_cols = (int)t->types.size();
+  if (!cols) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: cols is NULL");
+  if (!unique || ((uintptr_t)unique & 7) || ((uintptr_t)grouped & 7))
+    return set_error(DQ_E_INVALID, "dq_freq_unique_rows: the bitmaps must be 8-byte aligned device buffers");
+  auto is_str = [](int32_t ty) { return ty == DQ_TYPE_UTF8 || ty == DQ_TYPE_LARGE_UTF8; };
+  std::vector<int32_t> ty(t->types);
+  for (int c = 0; c < n_cols; ++c) {
+    if (types) ty[c] = types[c];
+    // the probe hashes what the build hashed: the same type, or a string column of the other offset width
+    if (ty[c] != t->types[c] && !(is_str(ty[c]) && is_str(t->types[c])))
+      return set_error(DQ_E_INVALID, "dq_freq_unique_rows: column %d has type %d, the table's has %d", c, ty[c], t->types[c]);
+    const dq_column_view& v = cols[c];
+    if (!v.values || ((uintptr_t)v.values & 3) || ((uintptr_t)v.validity & 3) || (is_str(ty[c]) && !v.offsets))
+      return set_error(DQ_E_INVALID, "dq_freq_unique_rows: column %d: missing or misaligned buffer", c);
+  }
+  DQ_HIP(hipSetDevice(t->device));
+  const hipStream_t S = reinterpret_cast<hipStream_t>(hip_stream);
+  const GroupCols g = view_cols(ty.data(), n_cols, cols, test_hash_mask(), true);
+  Frame fr(g_arena, t->device);
+  unsigned long long* d_out = nullptr;  // tot[2], then the missing flag
+  if (dq_status s = take(fr, d_out, 4)) return s;
+  DQ_HIP(hipMemsetAsync(d_out, 0, 4 * sizeof(unsigned long long), S));
+  const int64_t words = (n_rows + 63) / 64;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(8192, (words + 3) / 4));
+  with_bool(t->hashed != 0, [&](auto hashed) {
+    hipLaunchKernelGGL(unique_rows<decltype(hashed)::value>, dim3(grid), dim3(256), 0, S, g, n_rows, t->d_keys.get(),
+                       t->d_counts.get(), t->n_groups, unique, grouped, d_out, reinterpret_cast<int32_t*>(d_out + 2));
+  });
+  DQ_HIP(hipGetLastError());
+  unsigned long long h[4];
+  DQ_HIP(hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, S));
+  DQ_HIP(hipStreamSynchronize(S));
+  if (h[2]) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: a row whose key is no group of the table (built from other data)");
+  if (num_unique) *num_unique = (int64_t)h[0];
+  if (num_grouped) *num_grouped = (int64_t)h[1];
   return DQ_OK;
 }
 

@@ -1910,6 +1910,157 @@ __global__ __launch_bounds__(kBlock) void dq_pred_scan(const PredProgram* __rest
 }
 
 // ------------------------------------------------------------------------------------------
+// Row outcomes (dq_row_outcomes): dq_pred_scan's sibling that keeps the rows instead of counting them.  The same
+// program, atom loads, two-deep atom pipeline and logic ops; prog.counters[k] = output k's (predicate, where) root
+// slots.  At the end of a block word lane L holds 32 rows of every root: it stores, per output, the 32-bit word
+// pass = pred TRUE & where TRUE (and applies = where TRUE) at word index wr / 32 of the output's bitmap -- 16 lanes,
+// 64 consecutive bytes per output and 512-row wave step -- and adds the words' popcounts to the counter partials
+// (ct: pass, cn: applies), which leave as pred_counters_out's do.  The bitmaps are read as 64-bit words
+// (dq_take_index): the last range also stores the zero upper half of a last word whose rows end in its lower half.
+// ------------------------------------------------------------------------------------------
+struct RowOutputs {
+  uint32_t* pass[kMaxCounters];
+  uint32_t* applies[kMaxCounters];  // NULL: not wanted
+};
+
+__device__ __forceinline__ void row_block_out(const PredScratch& S, const PredCounter* s_ctr, int n_out,
+                                              const RowOutputs& out, int64_t wr, uint32_t inr, int64_t row1, int lane) {
+  if (lane >= 16) return;
+  // words of this range's part of the bitmaps: up to the 64-row boundary behind row1 (row1 is a multiple of 2048 in
+  // every range but the last, whose row1 is n_rows)
+  const bool store = wr < ((row1 + 63) & ~int64_t(63));
+  for (int c = 0; c < n_out; ++c) {
+    const PredCounter pc = s_ctr[c];
+    const uint32_t tw = (pc.where < 0 ? ~0u : S.rt[(pc.where) * 16 + lane]) & inr;
+    const uint32_t pw = S.rt[(pc.pred) * 16 + lane] & tw;
+    S.ct[(c) * 16 + lane] += __popc(pw);
+    S.cn[(c) * 16 + lane] += __popc(tw);
+    if (store) {
+      out.pass[c][wr >> 5] = pw;
+      if (out.applies[c]) out.applies[c][wr >> 5] = tw;
+    }
+  }
+}
+
+template <bool RX>
+__global__ __launch_bounds__(kBlock) void dq_row_outcomes_scan(const PredProgram* __restrict__ prog_g, ScanCols cols,
+                                                               RowOutputs out, int64_t n_rows, int64_t rows_per_range,
+                                                               PredPartial* __restrict__ acc) {
+  extern __shared__ uint32_t pred_lds[];
+  __shared__ PredInstr s_instr[kMaxInstr];
+  __shared__ uint32_t s_op[kMaxInstr];
+  __shared__ uint32_t s_ldw[kMaxInstr];
+  __shared__ PredCounter s_ctr[kMaxCounters];
+  const PredProgram& prog = *prog_g;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wave_words = 32 * (prog.stack_depth + prog.n_roots + prog.n_counters);
+  PredScratch S(pred_lds + wave * wave_words, prog.stack_depth, prog.n_roots, prog.n_counters);
+  const bool wl = lane < 16;
+  const int n_instr = prog.n_instr, n_out = prog.n_counters, n_loads = prog.n_loads;
+  for (int k = threadIdx.x; k < n_instr * (int)(sizeof(PredInstr) / 4); k += kBlock)
+    reinterpret_cast<uint32_t*>(s_instr)[k] = reinterpret_cast<const uint32_t*>(prog.instr)[k];
+  for (int k = threadIdx.x; k < n_instr; k += kBlock) s_op[k] = pred_op_word(prog.instr[k]);
+  for (int k = threadIdx.x; k < n_loads; k += kBlock) s_ldw[k] = pred_load_word(prog.instr[prog.load_instr[k]]);
+  for (int k = threadIdx.x; k < n_out; k += kBlock) s_ctr[k] = prog.counters[k];
+  __syncthreads();
+  if (wl) {
+    for (int c = 0; c < n_out; ++c) { S.ct[(c) * 16 + lane] = 0; S.cn[(c) * 16 + lane] = 0; }
+  }
+  uint16_t* dfa_lds = reinterpret_cast<uint16_t*>(pred_lds + kWaves * wave_words);
+  if (RX && prog.regex_words > 0) {
+    for (int k = threadIdx.x; k < prog.regex_words; k += kBlock) dfa_lds[k] = prog.regex[k];
+    __syncthreads();
+  }
+  const int64_t row0 = (int64_t)blockIdx.x * rows_per_range;
+  int64_t row1 = row0 + rows_per_range;
+  if (row1 > n_rows) row1 = n_rows;
+  AtomBuf B0, B1;
+  // (dq_pred_scan's issue: atom k's loads for the block at `base`, columns the other buffer holds copied)
+  auto issue = [&](int k, int64_t base, AtomBuf& L, const AtomBuf& C) {
+    const uint32_t lw = __builtin_amdgcn_readfirstlane(s_ldw[k]);
+    const int op = (int)(lw & 15u), col_a = (int)((lw >> 4) & 0xFFu) - 1, col_b = (int)((lw >> 12) & 0xFFu) - 1;
+    const int kind_a = (int)((lw >> 20) & 15u), kind_b = (int)((lw >> 24) & 15u);
+    const bool same_blk = C.t_base == base;
+    auto fetch = [&](int col, int kind, bool vals, uint64_t (&dst)[8], uint32_t& vdst) __attribute__((always_inline)) {
+      if (same_blk && col == C.t_col_a && (!vals || (C.t_vals && kind == C.t_kind_a))) {
+        if (vals) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dst[j] = C.a[j];
+        }
+        vdst = C.va;
+      } else if (same_blk && col == C.t_col_b && C.t_vals && (!vals || kind == C.t_kind_b)) {
+        if (vals) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dst[j] = C.b[j];
+        }
+        vdst = C.vb;
+      } else {
+        if (vals) pred_load(cols.values[col], kind, row0, row1, base, lane, dst);
+        vdst = pred_valid_word(cols.validity[col], base, n_rows, lane);
+      }
+    };
+    const bool cmp = op == PO_ATOM_CMP;
+    if (cmp && col_b >= 0) fetch(col_b, kind_b, true, L.b, L.vb);
+    fetch(col_a, kind_a, cmp, L.a, L.va);
+    L.t_base = base;
+    L.t_col_a = col_a;
+    L.t_col_b = cmp ? col_b : -1;
+    L.t_kind_a = kind_a;
+    L.t_kind_b = kind_b;
+    L.t_vals = cmp;
+  };
+  if (n_loads > 0) issue(0, row0 + (int64_t)wave * 512, B0, B1);
+  uint32_t g = 0;
+
+  for (int64_t blk = row0; blk < row1; blk += kRowsPerIter) {
+    const int64_t base = blk + (int64_t)wave * 512;
+    if (base >= row1) break;  // wave-uniform
+    const int64_t wr = base + 32 * (lane & 15);
+    const uint32_t inr = wr >= row1 ? 0u : (wr + 32 <= row1 ? ~0u : ((1u << (row1 - wr)) - 1u));
+    int sp = 0, k = 0;
+    for (int i = 0; i < n_instr; ++i) {
+      const uint32_t ow = __builtin_amdgcn_readfirstlane(s_op[i]);
+      const int op = (int)(ow & 0xFFu);
+      if (op == PO_ATOM_CMP || op == PO_ATOM_ISNULL || op == PO_ATOM_NOTNULL || op == PO_ATOM_REGEX) {
+        const int kn = k + 1 < n_loads ? k + 1 : 0;
+        const int64_t bn = k + 1 < n_loads ? base : base + kRowsPerIter;
+        uint32_t wt, wn;
+        if ((g & 1u) == 0) issue(kn, bn, B1, B0);
+        else issue(kn, bn, B0, B1);
+        if (op == PO_ATOM_CMP) {
+          const PredInstr ins = uniform_cmp_fields(&s_instr[i]);
+          if ((g & 1u) == 0) pred_atom_cmp(ins, B0, lane, wt, wn);
+          else pred_atom_cmp(ins, B1, lane, wt, wn);
+        } else if (RX && op == PO_ATOM_REGEX) {
+          const PredInstr ins = uniform_instr(&s_instr[i]);
+          const uint32_t va = (g & 1u) ? B1.va : B0.va;
+          if (ins.kind_a == CK_UTF8)
+            pred_atom_regex_utf8(ins, dfa_lds + ins.lit_i, reinterpret_cast<const uint8_t*>(cols.values[ins.col_a]),
+                                 reinterpret_cast<const int32_t*>(cols.offsets[ins.col_a]), n_rows, row1, base, lane,
+                                 va, wt, wn);
+          else
+            pred_atom_regex(ins, dfa_lds + ins.lit_i, reinterpret_cast<const uint8_t*>(cols.values[ins.col_a]),
+                            cols.offsets[ins.col_a], row1, base, lane, va, wt, wn);
+        } else {
+          const uint32_t va = (g & 1u) ? B1.va : B0.va;
+          wt = op == PO_ATOM_ISNULL ? ~va : va;
+          wn = 0u;
+        }
+        ++g;
+        ++k;
+        if (wl) { S.st[(sp) * 16 + lane] = wt; S.sn[(sp) * 16 + lane] = wn; }
+        ++sp;
+      } else {
+        pred_logic_op(ow, S, sp, lane);
+      }
+    }
+    row_block_out(S, s_ctr, n_out, out, wr, inr, row1, lane);
+  }
+  pred_counters_out(pred_lds, wave_words, prog, acc);
+}
+
+// ------------------------------------------------------------------------------------------
 // Kernel 4: fixed-order merge of per-workgroup partials into the plan accumulators.
 // blockIdx.x: [0, ncol) column tasks, [ncol, ncol + npair) pairs, then one block for counters (has_pred), then one
 // per HLL slot (nhll): the slot's floor for the next chunk's column scans (hll_floor_thr) -- every launch that
@@ -2038,6 +2189,25 @@ hipError_t launch_pred_scan(const PredProgram* prog, const ScanCols& cols, const
   else
     hipLaunchKernelGGL(dq_pred_scan<false>, dim3(nranges), dim3(kBlock), (size_t)lds_bytes, st, prog, cols, bm, n_rows,
                        rows_per_range, acc);
+  return hipGetLastError();
+}
+
+// dq_row_outcomes: pass / applies are the program's n_counters output bitmaps as 32-bit words (applies entries may
+// be NULL); acc: kPredAccCopies zeroed PredPartial copies (t: pass counts, nn: applies counts)
+hipError_t launch_row_outcomes(const PredProgram* prog, const ScanCols& cols, uint32_t* const* pass,
+                               uint32_t* const* applies, int32_t n_out, int64_t n_rows, int64_t rows_per_range,
+                               int32_t nranges, PredPartial* acc, int32_t lds_bytes, hipStream_t st, bool has_regex) {
+  RowOutputs out{};
+  for (int k = 0; k < n_out && k < kMaxCounters; ++k) {
+    out.pass[k] = pass[k];
+    out.applies[k] = applies ? applies[k] : nullptr;
+  }
+  if (has_regex)
+    hipLaunchKernelGGL(dq_row_outcomes_scan<true>, dim3(nranges), dim3(kBlock), (size_t)lds_bytes, st, prog, cols, out,
+                       n_rows, rows_per_range, acc);
+  else
+    hipLaunchKernelGGL(dq_row_outcomes_scan<false>, dim3(nranges), dim3(kBlock), (size_t)lds_bytes, st, prog, cols, out,
+                       n_rows, rows_per_range, acc);
   return hipGetLastError();
 }
 

@@ -41,7 +41,9 @@ extern "C" {
                                 dq_cast_utf8, the dq_cat_hist_* entry points, the dq_schema_* / dq_take_* / dq_split_*
                                 entry points and dq_pred_jit_drain are additions under 6 (nothing existing changed its layout or meaning);
                                 so are dq_freq_materialize / _self_contained / _to_bytes / _from_bytes / _take_values /
-                                _mutual_information (self-contained frequency tables) */
+                                _mutual_information (self-contained frequency tables) and the row-level results:
+                                dq_row_program_* / dq_row_outcomes (per-row predicate outcomes as bitmaps),
+                                dq_freq_unique_rows (the rows whose group has count 1) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -688,6 +690,52 @@ dq_status dq_take_index(const uint64_t* selection, int64_t n_rows, int64_t n_sel
 dq_status dq_take_rows(int32_t type, const dq_column_view* src, int64_t n_rows, const int64_t* index, int64_t n_selected,
                        void* out_values, int64_t values_capacity, uint8_t* out_validity, void* out_offsets,
                        int64_t* data_bytes, int32_t device, void* hip_stream);
+/* Row-level results (Deequ's VerificationResult.rowLevelResultsAsDataFrame): which rows pass, as bitmaps in the layout
+ * dq_take_index reads (64-bit words, LSB first, bit r = row r of the chunk, bits past n_rows written 0).
+ * A row program is a predicate program that keeps its rows: dq_row_program_create takes the column descriptors, the
+ * predicate pool and the regex patterns as dq_plan_create_ex does, plus n_out outputs (pred_root, where_root or -1).
+ * It lowers on the host and needs no device.  At most dq_row_max_outputs() outputs and as many distinct roots
+ * (predicates and `where` filters together), 64 columns and the fused pass's program length and DFA budget; a
+ * longer list is DQ_E_UNSUPPORTED: split it into several programs.  A root outside the GPU grammar is
+ * DQ_E_UNSUPPORTED as in dq_plan_create; a predicate over a DQ_TYPE_DICT_UTF8 column too (decode it).
+ * dq_row_outcomes evaluates one chunk of n_rows (< 2^31) on `device`, enqueued on hip_stream: cols are the chunk's
+ * views as dq_scan takes them (only the columns the program reads are looked at).  Output k writes
+ *   pass[k]      ceil(n_rows / 64) words: bit r = 1 iff pred is TRUE on row r and (no where, or where is TRUE on r);
+ *   applies[k]   (the array or an entry may be NULL: not wanted) bit r = 1 iff no where, or where is TRUE on row r;
+ *   num_pass[k] / num_applies[k] (host, either array may be NULL): the set bits of the two.
+ * A NULL predicate result is not a pass (Compliance's CASE WHEN p THEN 1 ELSE 0); a row whose where is NULL or FALSE
+ * neither passes nor applies.  No byte past ceil(n_rows / 64) * 8 of a bitmap is touched; pass / applies buffers
+ * are device memory, 8-byte aligned.  n_rows = 0: DQ_OK, nothing written (the counts are 0).  Invalid arguments are
+ * rejected before any launch.  Synchronises hip_stream.  Interpreted evaluator only (no compiled kernel).
+ * dq_row_program_info: the outputs, the distinct roots after deduplication and the program's instructions. */
+typedef struct dq_row_output {
+  int32_t pred_root;  /* root index into the predicate node pool */
+  int32_t where_root; /* optional `where` filter root, -1 = none */
+} dq_row_output;
+typedef struct dq_row_program dq_row_program;
+int32_t dq_row_max_outputs(void);
+dq_status dq_row_program_create(const dq_column_desc* schema, int32_t n_cols, const dq_pred_node* pred_pool,
+                                int32_t n_pred, const char* const* patterns, int32_t n_patterns,
+                                const dq_row_output* outputs, int32_t n_out, dq_row_program** out);
+dq_status dq_row_program_info(const dq_row_program* prog, int32_t* n_outputs, int32_t* n_roots, int32_t* n_instr);
+void dq_row_program_destroy(dq_row_program* prog);
+dq_status dq_row_outcomes(dq_row_program* prog, const dq_column_view* cols, int64_t n_rows, uint64_t* const* pass,
+                          uint64_t* const* applies, int32_t device, void* hip_stream, int64_t* num_pass,
+                          int64_t* num_applies);
+/* The unique rows of one chunk from a frequency table built (dq_freq_build / _build_weighted / _merge) from data that
+ * holds the chunk, over the table's grouping columns C.  cols: the chunk's views of C in the table's order; types:
+ * their type codes, or NULL for the table's own (a string column may have the other offset width: the key hashes
+ * bytes and length, so a dictionary column's table built from its entries is probed with the decoded column).
+ * unique: bit r = 1 iff every column of C is non-null in row r and the row's group has count 1; grouped (NULL: not
+ * wanted): bit r = 1 iff every column of C is non-null in row r (the row took part in the grouping).  Both in the
+ * bitmap layout above; *num_unique / *num_grouped (host, optional) their set bits.  A value that occurs once in
+ * this chunk and once in another chunk of the table's data is not unique.  Keys are computed as the build computed
+ * them and looked up in the table's sorted keys; the build verified that equal keys are equal tuples.  A row whose
+ * key the table lacks means the table was not built from this data: DQ_E_INVALID (the bitmaps' contents are then
+ * unspecified).  Runs on the table's device, enqueued on hip_stream, and synchronises it. */
+dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols, int64_t n_rows,
+                              uint64_t* unique, uint64_t* grouped, void* hip_stream, int64_t* num_unique,
+                              int64_t* num_grouped);
 /* Row-level random split (the train / test split of suggestions/ConstraintSuggestionRunner.scala:127-148).  Row r of
  * the chunk has the global index g = row0 + r; h = XXH64 of g's 8 little-endian bytes under `seed`,
  * u = (h >> 11) * 2^-53, and the row is a test row iff u < test_ratio, else a training row: a pure function of
