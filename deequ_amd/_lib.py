@@ -74,6 +74,11 @@ PRED_IS_NULL = 11
 PRED_IS_NOT_NULL = 12
 PRED_COALESCE = 13
 PRED_REGEX = 14
+PRED_EXPR = 15  # an arithmetic operand: a = index into the pool's expressions (dq_pred_pool_expr)
+
+# dq_expr_program (include/dqscan.h): limits and instruction set
+EXPR_MAX_COLUMNS, EXPR_MAX_INSTRS, EXPR_MAX_LITERALS, EXPR_MAX_STACK = 8, 32, 16, 8
+EXPR_COL, EXPR_LIT, EXPR_CAST, EXPR_NEG, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_DIV, EXPR_MOD = range(1, 10)
 
 REGEX_RLIKE = 0             # col RLIKE p: NULL on NULL, find()
 REGEX_EXTRACT_NONEMPTY = 1  # regexp_extract(col, p, 0) != '' as PatternMatch builds it: FALSE on NULL
@@ -102,6 +107,24 @@ PRED_PASS = {"auto": 0, "interpreter": 1, "compiled": 2}
 
 class PlanOptions(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int32), ("pred_pass", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+class ExprInstr(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("type", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class ExprLiteral(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int32), ("reserved", ctypes.c_int32), ("i64", ctypes.c_int64),
+                ("f64", ctypes.c_double)]
+
+
+class ExprProgram(ctypes.Structure):
+    _fields_ = [("n_instrs", ctypes.c_int32), ("n_columns", ctypes.c_int32), ("n_literals", ctypes.c_int32),
+                ("result_type", ctypes.c_int32), ("stack_depth", ctypes.c_int32), ("divides", ctypes.c_int32),
+                ("instrs", ExprInstr * EXPR_MAX_INSTRS), ("columns", ctypes.c_int32 * EXPR_MAX_COLUMNS),
+                ("column_types", ctypes.c_int32 * EXPR_MAX_COLUMNS), ("literals", ExprLiteral * EXPR_MAX_LITERALS),
+                ("text", ctypes.c_char_p)]
 
 
 class ColumnView(ctypes.Structure):
@@ -234,6 +257,15 @@ def _load():
     L.dq_pred_pool_num_patterns.argtypes = [c.c_void_p]
     L.dq_pred_pool_patterns.restype = P(c.c_char_p)
     L.dq_pred_pool_patterns.argtypes = [c.c_void_p]
+    L.dq_pred_pool_num_exprs.restype = c.c_int32
+    L.dq_pred_pool_num_exprs.argtypes = [c.c_void_p]
+    L.dq_pred_pool_expr.restype = P(ExprProgram)
+    L.dq_pred_pool_expr.argtypes = [c.c_void_p, c.c_int32]
+    L.dq_expr_eval.restype = c.c_int32
+    L.dq_expr_eval.argtypes = [P(ExprProgram), P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p, c.c_int32,
+                               c.c_void_p, P(c.c_int64)]
+    L.dq_expr_eval_host.restype = c.c_int32
+    L.dq_expr_eval_host.argtypes = [P(ExprProgram), P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p, P(c.c_int64)]
     L.dq_pred_pool_destroy.restype = None
     L.dq_pred_pool_destroy.argtypes = [c.c_void_p]
     L.dq_regex_match_host.restype = c.c_int32
@@ -431,6 +463,7 @@ EXPORTED = [
     "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
     "dq_row_max_outputs", "dq_row_program_create", "dq_row_program_info", "dq_row_program_destroy", "dq_row_outcomes",
     "dq_freq_unique_rows",
+    "dq_pred_pool_num_exprs", "dq_pred_pool_expr", "dq_expr_eval", "dq_expr_eval_host",
 ]
 
 

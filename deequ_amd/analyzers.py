@@ -80,11 +80,19 @@ class Preconditions:
 class PlanBuilder:
     """Collects the specs, referenced columns and predicate pool of one fused plan."""
 
-    def __init__(self, table_schema, length_columns: Optional[dict] = None):
+    def __init__(self, table_schema, length_columns: Optional[dict] = None, expr_columns: Optional[dict] = None,
+                 collect_exprs: bool = False):
         self.table_schema = list(table_schema)
         self.by_name = {c[0]: c for c in self.table_schema}
         # source string column -> the derived length column the runner attached (lengths.attach_length_columns)
         self.length_columns = dict(length_columns or {})
+        # canonical arithmetic expression -> the derived column the runner attached
+        # (expressions.attach_expression_columns); exprs: the expressions the predicates added so far hold.
+        # collect_exprs: only find them -- an expression without a derived column stays a DQ_PRED_EXPR node, and
+        # the builder is good for nothing but reading `exprs`
+        self.expr_columns = dict(expr_columns or {})
+        self.collect_exprs = collect_exprs
+        self.exprs: dict = {}
         self.columns: List[str] = []
         self.pool = PredicatePool(self)
         self.specs: List[tuple] = []
@@ -105,6 +113,19 @@ class PlanBuilder:
                 f"no derived length column of {name} in this plan: MinLength / MaxLength run through AnalysisRunner "
                 "or runner.scan_states, which attach it (lengths.attach_length_columns)")
         return self.col(self.length_columns[name])
+
+    def expr_col(self, e) -> Optional[int]:
+        """The plan column of the derived column of expression `e` (expressions.Expression); None while only
+        collecting.  The expression's source columns do not enter the plan."""
+        self.exprs.setdefault(e.text, e)
+        name = self.expr_columns.get(e.text)
+        if name is None or name not in self.by_name:
+            if self.collect_exprs:
+                return None
+            raise UnsupportedOnGpuPathException(
+                f"no derived column of {e.text} in this plan: predicates with arithmetic run through AnalysisRunner, "
+                "runner.scan_states or row_level_results, which attach it (expressions.attach_expression_columns)")
+        return self.col(name)
 
     def pred(self, text: Optional[str]) -> int:
         return -1 if text is None else self.pool.add(text)

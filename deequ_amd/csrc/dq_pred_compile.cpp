@@ -12,9 +12,16 @@
 //     not      := NOT not | cmp
 //     cmp      := operand ( (< | <= | > | >= | = | == | != | <>) operand | IS [NOT] NULL
 //                           | [NOT] IN ('s', ...) )?
-//     operand  := column | `column` | number | - number | NULL | TRUE | FALSE | 'string'
-//               | COALESCE(operand, operand) | ( expr )
+//     operand  := sum
+//     sum      := term ( (+ | -) term )*
+//     term     := unary ( (* | / | %) unary )*
+//     unary    := - unary | primary
+//     primary  := column | `column` | number | - number | NULL | TRUE | FALSE | 'string'
+//               | COALESCE(primary, primary) | ( expr )      (COALESCE also takes `- number`)
 //
+// A sum that is one primary lowers as it always did.  One with an operator and a column becomes a DQ_PRED_EXPR node
+// over a postfix dq_expr_program (include/dqscan.h states the Spark 2.2 typing and the refusals): the caller
+// materialises it as a derived column, so the plan and its kernels never see arithmetic.
 // Literal typing follows Spark 2.2: `3` integer, `3.0` exact decimal (unscaled int64 + scale), `3e0`
 // double.  String (in)equality and IN lists compare the UTF-8 bytes of a string column with the literals:
 // they lower to a whole-value DFA (DQ_PRED_REGEX, mode DQ_REGEX_FULL) over the escaped literals.  Anything
@@ -27,6 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -41,6 +49,11 @@ struct dq_pred_pool {
   std::vector<dq_pred_node> nodes;
   std::vector<std::string> patterns;
   std::vector<const char*> pattern_ptrs;
+  struct Expr {
+    std::string text;  // canonical
+    dq_expr_program prog;
+  };
+  std::vector<std::unique_ptr<Expr>> exprs;
 };
 
 namespace {
@@ -125,7 +138,7 @@ std::vector<Tok> tokenize(const std::string& s) {
                s.compare(i, 2, "<>") == 0 || s.compare(i, 2, "==") == 0) {
       toks.push_back({T_OP, s.substr(i, 2)});
       i += 2;
-    } else if (std::strchr("<>=(),-", c) && c != '\0') {
+    } else if (std::strchr("<>=(),-+*/%", c) && c != '\0') {
       toks.push_back({T_OP, std::string(1, c)});
       ++i;
     } else {
@@ -145,12 +158,39 @@ int32_t cmp_of(const std::string& op) {
   return 0;
 }
 
-// An operand: a node index, or (string literals) the literal text, valid only beside a string column.
+// An arithmetic operand before it is lowered: leaves are columns and literals, inner nodes dq_expr_op operators.
+struct Ast {
+  int32_t op = 0;         // DQ_EXPR_COL / DQ_EXPR_LIT leaf, DQ_EXPR_NEG (l), DQ_EXPR_ADD .. DQ_EXPR_MOD (l, r)
+  int32_t col = -1;       // COL: position in the pool's column list
+  int32_t lit_kind = 0;   // LIT: DQ_PRED_LIT_INT / _DECIMAL / _DOUBLE
+  int32_t scale = 0;      // LIT decimal
+  int64_t i64 = 0;
+  double f64 = 0.0;
+  int32_t type = 0;       // enum dq_type, set by Parser::type_of (0 for a decimal literal not yet placed)
+  std::shared_ptr<Ast> l, r;
+};
+using AstP = std::shared_ptr<Ast>;
+
+// An operand: a node index, or (string literals) the literal text, valid only beside a string column, or an
+// arithmetic expression that its consumer (a comparison, IS [NOT] NULL) lowers to a DQ_PRED_EXPR node.
 struct Operand {
   int32_t node = -1;
   bool is_str = false;
   std::string str;
+  AstP ast;
 };
+
+int type_rank(int32_t t) {  // Byte < Short < Int < Long < Float < Double; 0: not a type arithmetic takes
+  switch (t) {
+    case DQ_TYPE_I8: return 1;
+    case DQ_TYPE_I16: return 2;
+    case DQ_TYPE_I32: return 3;
+    case DQ_TYPE_I64: return 4;
+    case DQ_TYPE_F32: return 5;
+    case DQ_TYPE_F64: return 6;
+    default: return 0;
+  }
+}
 
 class Parser {
  public:
@@ -159,8 +199,7 @@ class Parser {
   int32_t parse() {
     const Operand r = parse_or();
     if (pos != toks.size()) unsupported("unsupported syntax near '%s' in '%s'", toks[pos].text.c_str(), text.c_str());
-    if (r.is_str) unsupported("bare string literal in '%s'", text.c_str());
-    return r.node;
+    return need_node(r);
   }
 
  private:
@@ -194,6 +233,7 @@ class Parser {
   }
   int32_t need_node(const Operand& o) {
     if (o.is_str) unsupported("bare string literal in '%s'", text.c_str());
+    if (o.ast) unsupported("arithmetic expression used as a boolean or as an argument in '%s'", text.c_str());
     return o.node;
   }
 
@@ -237,11 +277,15 @@ class Parser {
   }
 
   Operand parse_cmp() {
-    Operand a = parse_operand();
+    Operand a = parse_sum();
     const Tok t = peek();
     if (t.kind == T_OP && cmp_of(t.text)) {
       take();
-      Operand b = parse_operand();
+      Operand b = parse_sum();
+      if ((a.is_str || b.is_str) && (a.ast || b.ast))
+        unsupported("string literal compared with an arithmetic expression in '%s'", text.c_str());
+      if (a.ast) a = node(lower(a.ast));
+      if (b.ast) b = node(lower(b.ast));
       if (a.is_str || b.is_str) {  // string (in)equality
         if (t.text != "=" && t.text != "==" && t.text != "!=" && t.text != "<>")
           unsupported("string ordering comparison in '%s'", text.c_str());
@@ -268,6 +312,7 @@ class Parser {
         return a;
       }
       if (neg) take();
+      if (a.ast) unsupported("IN over an arithmetic expression in '%s'", text.c_str());
       expect(T_OP, "(");
       std::vector<Tok> items{take()};
       while (at(T_OP, ",")) {
@@ -291,6 +336,7 @@ class Parser {
         neg = true;
       }
       expect(T_KW, "NULL");
+      if (a.ast) a = node(lower(a.ast));
       return node(add(neg ? DQ_PRED_IS_NOT_NULL : DQ_PRED_IS_NULL, need_node(a)));
     }
     if (t.kind == T_KW && (t.text == "LIKE" || t.text == "RLIKE" || t.text == "BETWEEN"))
@@ -323,17 +369,223 @@ class Parser {
     return root;
   }
 
+  // ---- arithmetic operands -------------------------------------------------------------------------------------
+  // The leaf nodes of a sum with an operator were appended to the pool while its primaries were parsed; the sum
+  // takes them back (the pool holds only the DQ_PRED_EXPR node its consumer appends).
+  Operand parse_sum() {
+    const size_t n0 = P.nodes.size();
+    Operand a = parse_term();
+    while (at(T_OP, "+") || at(T_OP, "-")) {
+      const int32_t op = take().text == "+" ? DQ_EXPR_ADD : DQ_EXPR_SUB;
+      const AstP l = as_ast(a);
+      a = binary(op, l, as_ast(parse_term()));
+    }
+    if (a.ast) P.nodes.resize(n0);
+    return a;
+  }
+  Operand parse_term() {
+    Operand a = parse_unary();
+    while (at(T_OP, "*") || at(T_OP, "/") || at(T_OP, "%")) {
+      const std::string o = take().text;
+      const AstP l = as_ast(a);
+      a = binary(o == "*" ? DQ_EXPR_MUL : o == "/" ? DQ_EXPR_DIV : DQ_EXPR_MOD, l, as_ast(parse_unary()));
+    }
+    return a;
+  }
+  Operand parse_unary() {
+    if (!at(T_OP, "-")) return parse_operand();
+    take();
+    if (peek().kind == T_NUM) return node(number("-" + take().text));  // `- number` is a literal
+    if (++minus_depth > 64) unsupported("unary minus nested too deeply in '%s'", text.c_str());
+    const AstP x = as_ast(parse_unary());
+    --minus_depth;
+    Operand o;
+    o.ast = std::make_shared<Ast>();
+    o.ast->op = DQ_EXPR_NEG;
+    o.ast->l = x;
+    return o;
+  }
+  int minus_depth = 0;
+
+  Operand binary(int32_t op, const AstP& l, const AstP& r) {
+    Operand o;
+    o.ast = std::make_shared<Ast>();
+    o.ast->op = op;
+    o.ast->l = l;
+    o.ast->r = r;
+    return o;
+  }
+
+  // an operand of an arithmetic operator: an expression as it is, a column or numeric literal node as a leaf
+  AstP as_ast(const Operand& o) {
+    if (o.ast) return o.ast;
+    if (o.is_str) unsupported("string operand of an arithmetic operator in '%s'", text.c_str());
+    const dq_pred_node& x = P.nodes[(size_t)o.node];
+    AstP a = std::make_shared<Ast>();
+    switch (x.kind) {
+      case DQ_PRED_COLUMN: {
+        const int32_t t = P.types[(size_t)x.a];
+        const char* name = P.names[(size_t)x.a].c_str();
+        if (DQ_TYPE_BASE(t) == DQ_TYPE_DECIMAL128)
+          unsupported("decimal column '%s' inside arithmetic in '%s'", name, text.c_str());
+        if (!type_rank(t)) unsupported("non-numeric column '%s' inside arithmetic in '%s'", name, text.c_str());
+        a->op = DQ_EXPR_COL;
+        a->col = x.a;
+        a->type = t;
+        return a;
+      }
+      case DQ_PRED_LIT_INT:
+      case DQ_PRED_LIT_DECIMAL:
+      case DQ_PRED_LIT_DOUBLE:
+        a->op = DQ_EXPR_LIT;
+        a->lit_kind = x.kind;
+        a->i64 = x.i64;
+        a->f64 = x.f64;
+        a->scale = x.cmp;
+        return a;
+      case DQ_PRED_LIT_NULL: unsupported("NULL inside arithmetic in '%s'", text.c_str());
+      case DQ_PRED_LIT_BOOL: unsupported("boolean operand of an arithmetic operator in '%s'", text.c_str());
+      case DQ_PRED_COALESCE: unsupported("COALESCE inside arithmetic in '%s'", text.c_str());
+      default: unsupported("boolean operand of an arithmetic operator in '%s'", text.c_str());
+    }
+  }
+
+  // The Spark type of every node.  A decimal literal has a type only beside a Float / Double operand (it is cast
+  // to Double); anywhere else the operation would be decimal arithmetic.
+  bool is_decimal_lit(const AstP& a) const { return a->op == DQ_EXPR_LIT && a->lit_kind == DQ_PRED_LIT_DECIMAL; }
+  int32_t type_of(const AstP& a) {
+    switch (a->op) {
+      case DQ_EXPR_COL: return a->type;
+      case DQ_EXPR_LIT:
+        if (a->lit_kind == DQ_PRED_LIT_DOUBLE) a->type = DQ_TYPE_F64;
+        else if (a->lit_kind == DQ_PRED_LIT_INT) a->type = a->i64 >= INT32_MIN && a->i64 <= INT32_MAX ? DQ_TYPE_I32 : DQ_TYPE_I64;
+        else unsupported("decimal literal outside a Float / Double operation (decimal arithmetic) in '%s'", text.c_str());
+        return a->type;
+      case DQ_EXPR_NEG: return a->type = type_of(a->l);
+      default: break;
+    }
+    int32_t tl, tr;
+    if (is_decimal_lit(a->l) && is_decimal_lit(a->r))
+      unsupported("arithmetic on two decimal literals (decimal arithmetic) in '%s'", text.c_str());
+    if (is_decimal_lit(a->l) || is_decimal_lit(a->r)) {
+      const AstP& lit = is_decimal_lit(a->l) ? a->l : a->r;
+      const int32_t other = type_of(is_decimal_lit(a->l) ? a->r : a->l);
+      if (other != DQ_TYPE_F32 && other != DQ_TYPE_F64)
+        unsupported("decimal literal combined with an integral operand (decimal arithmetic) in '%s'", text.c_str());
+      // the literal's double: its digits read as a double are the correctly rounded value of unscaled / 10^scale
+      char buf[64];
+      std::snprintf(buf, sizeof(buf), "%lldE-%d", (long long)lit->i64, (int)lit->scale);
+      lit->f64 = std::strtod(buf, nullptr);
+      lit->lit_kind = DQ_PRED_LIT_DOUBLE;
+      lit->type = DQ_TYPE_F64;
+      tl = a->l == lit ? DQ_TYPE_F64 : other;
+      tr = a->r == lit ? DQ_TYPE_F64 : other;
+    } else {
+      tl = type_of(a->l);
+      tr = type_of(a->r);
+    }
+    a->type = a->op == DQ_EXPR_DIV ? DQ_TYPE_F64 : (type_rank(tl) >= type_rank(tr) ? tl : tr);
+    return a->type;
+  }
+
+  struct Emit {
+    dq_expr_program p{};
+    int depth = 0;
+    std::string why;
+  };
+  void push_instr(Emit& e, int32_t op, int32_t arg, int32_t type, int delta) {
+    if (e.p.n_instrs >= DQ_EXPR_MAX_INSTRS)
+      unsupported("arithmetic expression longer than %d instructions in '%s'", DQ_EXPR_MAX_INSTRS, text.c_str());
+    e.p.instrs[e.p.n_instrs++] = dq_expr_instr{op, arg, type, 0};
+    e.depth += delta;
+    if (e.depth > DQ_EXPR_MAX_STACK)
+      unsupported("arithmetic expression nested deeper than a %d-entry value stack in '%s'", DQ_EXPR_MAX_STACK, text.c_str());
+    if (e.depth > e.p.stack_depth) e.p.stack_depth = e.depth;
+  }
+  void emit(Emit& e, const AstP& a, int32_t want) {
+    switch (a->op) {
+      case DQ_EXPR_COL: {
+        int32_t k = 0;
+        while (k < e.p.n_columns && e.p.columns[k] != a->col) ++k;
+        if (k == e.p.n_columns) {
+          if (k >= DQ_EXPR_MAX_COLUMNS)
+            unsupported("arithmetic expression over more than %d columns in '%s'", DQ_EXPR_MAX_COLUMNS, text.c_str());
+          e.p.columns[k] = a->col;
+          e.p.column_types[k] = a->type;
+          ++e.p.n_columns;
+        }
+        push_instr(e, DQ_EXPR_COL, k, a->type, 1);
+        break;
+      }
+      case DQ_EXPR_LIT: {
+        if (e.p.n_literals >= DQ_EXPR_MAX_LITERALS)
+          unsupported("arithmetic expression with more than %d literals in '%s'", DQ_EXPR_MAX_LITERALS, text.c_str());
+        const bool dbl = a->type == DQ_TYPE_F64;
+        e.p.literals[e.p.n_literals] = dq_expr_literal{a->type, 0, dbl ? 0 : a->i64, dbl ? a->f64 : 0.0};
+        push_instr(e, DQ_EXPR_LIT, e.p.n_literals++, a->type, 1);
+        break;
+      }
+      case DQ_EXPR_NEG:
+        emit(e, a->l, a->type);
+        push_instr(e, DQ_EXPR_NEG, 0, a->type, 0);
+        break;
+      default: {
+        emit(e, a->l, a->type);
+        emit(e, a->r, a->type);
+        push_instr(e, a->op, 0, a->type, -1);
+        if (a->op == DQ_EXPR_DIV || a->op == DQ_EXPR_MOD) e.p.divides = 1;
+      }
+    }
+    if (want != a->type) push_instr(e, DQ_EXPR_CAST, 0, want, 0);
+  }
+
+  bool has_column(const AstP& a) const {
+    return a->op == DQ_EXPR_COL || (a->l && has_column(a->l)) || (a->r && has_column(a->r));
+  }
+  std::string canonical(const AstP& a) const {
+    char buf[64];
+    switch (a->op) {
+      case DQ_EXPR_COL: return "`" + P.names[(size_t)a->col] + "`";
+      case DQ_EXPR_LIT:
+        if (a->type != DQ_TYPE_F64) {
+          std::snprintf(buf, sizeof(buf), "%lld", (long long)a->i64);
+          return buf;
+        }
+        std::snprintf(buf, sizeof(buf), "%.17g", a->f64);
+        return std::strpbrk(buf, "en") ? std::string(buf) : std::string(buf) + "e0";  // (e: exponent, n: inf / nan)
+      case DQ_EXPR_NEG: return "(-" + canonical(a->l) + ")";
+      default: {
+        static const char* const sym[] = {"+", "-", "*", "/", "%"};
+        return "(" + canonical(a->l) + " " + sym[a->op - DQ_EXPR_ADD] + " " + canonical(a->r) + ")";
+      }
+    }
+  }
+
+  // the DQ_PRED_EXPR node of an arithmetic operand; equal canonical texts share one entry of the pool
+  int32_t lower(const AstP& a) {
+    if (!has_column(a)) unsupported("arithmetic on literals alone (no column) in '%s'", text.c_str());
+    const int32_t type = type_of(a);
+    Emit e;
+    emit(e, a, type);
+    e.p.result_type = type;
+    const std::string canon = canonical(a);
+    size_t idx = 0;
+    while (idx < P.exprs.size() && P.exprs[idx]->text != canon) ++idx;
+    if (idx == P.exprs.size()) {
+      P.exprs.push_back(std::make_unique<dq_pred_pool::Expr>());
+      P.exprs.back()->text = canon;
+      P.exprs.back()->prog = e.p;
+      P.exprs.back()->prog.text = P.exprs.back()->text.c_str();
+    }
+    return add(DQ_PRED_EXPR, (int32_t)idx, -1, type);
+  }
+
   Operand parse_operand() {
     const Tok t = take();
     if (t.kind == T_OP && t.text == "(") {
       Operand e = parse_or();
       expect(T_OP, ")");
       return e;
-    }
-    if (t.kind == T_OP && t.text == "-") {
-      const Tok t2 = take();
-      if (t2.kind != T_NUM) unsupported("unary minus on a non-literal in '%s'", text.c_str());
-      return node(number("-" + t2.text));
     }
     if (t.kind == T_NUM) return node(number(t.text));
     if (t.kind == T_STR) {
@@ -347,9 +599,9 @@ class Parser {
       return node(add(DQ_PRED_LIT_BOOL, -1, -1, 0, t.text == "TRUE" ? 1 : 0));
     if (t.kind == T_KW && t.text == "COALESCE") {
       expect(T_OP, "(");
-      const int32_t a = need_node(parse_operand());
+      const int32_t a = need_node(parse_unary());  // (a primary or `- number`: arithmetic is refused here)
       expect(T_OP, ",");
-      const int32_t b = need_node(parse_operand());
+      const int32_t b = need_node(parse_unary());
       if (at(T_OP, ",")) unsupported("COALESCE with more than two arguments in '%s'", text.c_str());
       expect(T_OP, ")");
       return node(add(DQ_PRED_COALESCE, a, b));
@@ -429,7 +681,7 @@ dq_status dq_pred_pool_create(const char* const* names, const int32_t* types, in
 
 dq_status dq_pred_pool_add(dq_pred_pool* pool, const char* sql, int32_t* root) {
   if (!pool || !sql || !root) return dq::set_error(DQ_E_INVALID, "dq_pred_pool_add: bad argument");
-  const size_t n0 = pool->nodes.size(), np0 = pool->patterns.size();
+  const size_t n0 = pool->nodes.size(), np0 = pool->patterns.size(), ne0 = pool->exprs.size();
   try {
     const std::string text(sql);
     Parser ps(*pool, text);
@@ -439,6 +691,7 @@ dq_status dq_pred_pool_add(dq_pred_pool* pool, const char* sql, int32_t* root) {
     pool->nodes.resize(n0);  // the pool is unchanged by a failed add
     pool->patterns.resize(np0);
     pool->pattern_ptrs.resize(np0);
+    pool->exprs.resize(ne0);
     return dq::set_error(e.status, "%s", e.msg.c_str());
   }
 }
@@ -470,6 +723,10 @@ const dq_pred_node* dq_pred_pool_nodes(const dq_pred_pool* pool) {
 int32_t dq_pred_pool_num_patterns(const dq_pred_pool* pool) { return pool ? (int32_t)pool->patterns.size() : 0; }
 const char* const* dq_pred_pool_patterns(const dq_pred_pool* pool) {
   return pool && !pool->pattern_ptrs.empty() ? pool->pattern_ptrs.data() : nullptr;
+}
+int32_t dq_pred_pool_num_exprs(const dq_pred_pool* pool) { return pool ? (int32_t)pool->exprs.size() : 0; }
+const dq_expr_program* dq_pred_pool_expr(const dq_pred_pool* pool, int32_t index) {
+  return pool && index >= 0 && (size_t)index < pool->exprs.size() ? &pool->exprs[(size_t)index]->prog : nullptr;
 }
 void dq_pred_pool_destroy(dq_pred_pool* pool) { delete pool; }
 

@@ -174,6 +174,7 @@ def attach_length_columns(data: Union[Table, Sequence[Table]], analyzers: Sequen
             derived.append(col)
         out = Table(list(t.columns.values()) + derived)
         out.length_columns = dict(names)
+        out.expr_columns = dict(t.expr_columns)
         return out
 
     return one(data) if isinstance(data, Table) else [one(t) for t in chunks]

@@ -12,14 +12,23 @@ binds it and maps plan columns.  It stands in for Spark's `expr(...)` at the bou
     not      := NOT not | cmp
     cmp      := operand ( (< | <= | > | >= | = | == | != | <>) operand | IS [NOT] NULL
                           | [NOT] IN ('string', ...) )?
-    operand  := column | `column` | number | - number | NULL | TRUE | FALSE | 'string'
-              | COALESCE(operand, operand) | ( expr )
+    operand  := sum
+    sum      := term ( (+ | -) term )*
+    term     := unary ( (* | / | %) unary )*
+    unary    := - unary | primary
+    primary  := column | `column` | number | - number | NULL | TRUE | FALSE | 'string'
+              | COALESCE(primary, primary) | ( expr )
 
 Literal typing follows Spark 2.2: `3` integer, `3.0` exact decimal, `3e0` double.  String (in)equality
 and IN lists on a string column lower to a whole-value DFA (DQ_PRED_REGEX, mode DQ_REGEX_FULL).
-Anything else (string ordering, numeric comparison of a string column, LIKE, RLIKE, functions, literals
-with backslash escapes) raises UnsupportedPredicate: such an analyzer is routed to the fallback set,
-exactly like a type the GPU plan does not cover.
+An operand with an arithmetic operator and a column (`a * b + c`, `id % 2`, `a / b`) is a DQ_PRED_EXPR node
+over a postfix program (dqscan.h states the Spark 2.2 typing, wrapping, NULL and division rules):
+expressions.py materialises it once per chunk as a derived column (dq_expr_eval) and _sync hands the node to
+the plan as DQ_PRED_COLUMN of that column, so the plan's comparison rules apply to the result unchanged.
+Anything else (string ordering, numeric comparison of a string column, LIKE, RLIKE, BETWEEN, functions,
+literals with backslash escapes, arithmetic on decimal / non-numeric operands or on literals alone) raises
+UnsupportedPredicate: such an analyzer is routed to the fallback set, exactly like a type the GPU plan does
+not cover.
 """
 from __future__ import annotations
 
@@ -56,6 +65,7 @@ class PredicatePool:
         self._h = h
         self.nodes: List[Tuple[int, int, int, int, int, float]] = []
         self.patterns: List[str] = []  # DQ_PRED_REGEX patterns (dq_plan_create_ex)
+        self.exprs: list = []  # the C pool's expression list (expressions.Expression), DQ_PRED_EXPR nodes' `a`
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -65,14 +75,30 @@ class PredicatePool:
 
     def _sync(self) -> None:
         """Mirror the nodes / patterns the C pool appended, plan column indices in place of table ones."""
+        from .expressions import expression_from_pool
+
         n = L.lib.dq_pred_pool_size(self._h)
         base = L.lib.dq_pred_pool_nodes(self._h)
+        for k in range(len(self.exprs), L.lib.dq_pred_pool_num_exprs(self._h)):
+            self.exprs.append(expression_from_pool(self._h, k, self._names))
+        missing = None
         for i in range(len(self.nodes), n):
             x = base[i]
-            a = x.a
-            if x.kind == L.PRED_COLUMN:
+            kind, a, cmp = x.kind, x.a, x.cmp
+            if kind == L.PRED_COLUMN:
                 a = self.b.col(self._names[x.a])
-            self.nodes.append((x.kind, a, x.b, x.cmp, x.i64, x.f64))
+            elif kind == L.PRED_EXPR:
+                # an arithmetic operand: the plan reads its derived column (the builder refuses when the data
+                # carries none; while only collecting the node stays as it is)
+                try:
+                    col = self.b.expr_col(self.exprs[x.a])
+                except Exception as e:  # (the mirror stays whole; a plan refuses the node's kind)
+                    col, missing = None, e
+                if col is not None:
+                    kind, a, cmp = L.PRED_COLUMN, col, 0
+            self.nodes.append((kind, a, x.b, cmp, x.i64, x.f64))
+        if missing is not None:
+            raise missing
         npat = L.lib.dq_pred_pool_num_patterns(self._h)
         pats = L.lib.dq_pred_pool_patterns(self._h)
         self.patterns = [pats[i].decode("utf-8") for i in range(npat)]

@@ -86,9 +86,9 @@ def row_form(constraint) -> Union[RowForm, str]:
 class RowProgram:
     """One dq_row_program over its own plan columns (host object; the device copy is made by its first evaluation)."""
 
-    def __init__(self, forms: Sequence[RowForm], schema):
+    def __init__(self, forms: Sequence[RowForm], schema, expr_columns: Optional[dict] = None):
         self.forms = list(forms)
-        b = PlanBuilder(schema)
+        b = PlanBuilder(schema, None, expr_columns)
         cache: Dict[tuple, int] = {}
 
         def root(r: tuple) -> int:
@@ -177,6 +177,9 @@ class RowLevelPlan:
     programs: List[RowProgram]
     skipped: List[Tuple[str, str]]
     schema: list = field(default_factory=list)
+    # canonical arithmetic expression -> the derived column the programs read (expressions.derived_schema); `schema`
+    # holds those columns
+    expr_columns: Dict[str, str] = field(default_factory=dict)
 
     def program_of(self, key: str) -> Tuple[int, int]:
         """(program, output) of a predicate form."""
@@ -197,7 +200,7 @@ def _plain_schema(schema):
     return [(n, "utf8" if dt == "dict_utf8" else dt, nl) for n, dt, nl in schema]
 
 
-def _split_programs(forms: List[RowForm], schema, cap: int) -> List[RowProgram]:
+def _split_programs(forms: List[RowForm], schema, cap: int, expr_columns: Optional[dict] = None) -> List[RowProgram]:
     """Greedy split: a program takes outputs while it holds at most `cap` outputs and `cap` distinct roots; a group
     the library still refuses for its size (program length, DFA budget, columns) is halved."""
     groups: List[List[RowForm]] = []
@@ -216,7 +219,7 @@ def _split_programs(forms: List[RowForm], schema, cap: int) -> List[RowProgram]:
 
     def build(group: List[RowForm]) -> None:
         try:
-            out.append(RowProgram(group, schema))
+            out.append(RowProgram(group, schema, expr_columns))
         except UnsupportedPredicate:
             if len(group) == 1:
                 raise
@@ -228,10 +231,27 @@ def _split_programs(forms: List[RowForm], schema, cap: int) -> List[RowProgram]:
     return out
 
 
-def plan_row_level(checks, schema, max_outputs_per_program: Optional[int] = None) -> RowLevelPlan:
+def _sql_texts(checks) -> List[str]:
+    """The predicate and `where` texts of the checks' row-level forms."""
+    out: List[str] = []
+    for check in checks:
+        for c in check.constraints:
+            f = row_form(c)
+            if not isinstance(f, str) and f.kind == "predicate":
+                out += [r[1] for r in f.roots() if r[0] == "sql"]
+    return list(dict.fromkeys(out))
+
+
+def plan_row_level(checks, schema, max_outputs_per_program: Optional[int] = None,
+                   expr_columns: Optional[dict] = None) -> RowLevelPlan:
     """Host-only planning: which constraints get a row-level form, their keys and roots, the skipped ones with their
-    reasons, and the split of the predicate forms into row programs."""
+    reasons, and the split of the predicate forms into row programs.  Arithmetic operands of the predicates are
+    planned as the derived columns an evaluation attaches for them (expr_columns: those the data carries already)."""
+    from .expressions import derived_schema, text_expressions
+
+    checks = list(checks)
     schema = _plain_schema(schema)
+    schema, expr_columns = derived_schema(text_expressions(_sql_texts(checks), schema), schema, expr_columns)
     names = {c[0] for c in schema}
     cap = max_outputs() if max_outputs_per_program is None else min(int(max_outputs_per_program), max_outputs())
     per_check: List[Tuple[str, List[str]]] = []
@@ -253,7 +273,7 @@ def plan_row_level(checks, schema, max_outputs_per_program: Optional[int] = None
                         continue
                 else:
                     try:  # alone first: what the GPU grammar (or the device stack) does not take is skipped, with the reason
-                        RowProgram([f], schema).close()
+                        RowProgram([f], schema, expr_columns).close()
                     except UnsupportedPredicate as e:
                         skipped.append((key, f"UnsupportedPredicate: {e}"))
                         continue
@@ -263,8 +283,8 @@ def plan_row_level(checks, schema, max_outputs_per_program: Optional[int] = None
                 forms[key] = f
             keys.append(key)
         per_check.append((check.description, keys))
-    programs = _split_programs([f for f in forms.values() if f.kind == "predicate"], schema, cap)
-    return RowLevelPlan(per_check, forms, programs, skipped, list(schema))
+    programs = _split_programs([f for f in forms.values() if f.kind == "predicate"], schema, cap, expr_columns)
+    return RowLevelPlan(per_check, forms, programs, skipped, list(schema), dict(expr_columns))
 
 
 # ---- outcomes ------------------------------------------------------------------------------------------------------
@@ -445,17 +465,24 @@ def row_level_results(checks, data, filteredRow: str = "TRUE") -> RowLevelResult
     chunks = [data] if isinstance(data, Table) else list(data)
     if not chunks:
         raise ValueError("row_level_results: no chunks")
-    plan = plan_row_level(checks, chunks[0].schema)
+    # the derived columns of the predicates' arithmetic operands: one per distinct expression, once per chunk, on
+    # tables of this call's own (the outcomes and the row takes refer to the caller's chunks)
+    from .expressions import attach_expression_columns, text_expressions
+
+    pred_chunks, failed = attach_expression_columns(chunks, text_expressions(_sql_texts(checks), chunks[0].schema))
+    if failed:
+        raise next(iter(failed.values()))
+    plan = plan_row_level(checks, pred_chunks[0].schema, expr_columns=pred_chunks[0].expr_columns)
     # the dictionary-encoded columns a predicate or pattern touches: read through their decoded columns
     touched = {c for prog in plan.programs for c in prog.columns}
     dict_cols = {n for n, dt, _ in chunks[0].schema if dt == "dict_utf8"} & touched
-    pred_chunks = chunks
     if dict_cols:
-        pred_chunks = plain_utf8(chunks, dict_cols)
-        if _plain_schema(chunks[0].schema) != list(pred_chunks[0].schema):  # (large_utf8 entries)
+        before = _plain_schema(pred_chunks[0].schema)
+        pred_chunks = plain_utf8(pred_chunks, dict_cols)
+        if before != list(pred_chunks[0].schema):  # (large_utf8 entries)
             for prog in plan.programs:
                 prog.close()
-            plan = plan_row_level(checks, pred_chunks[0].schema)
+            plan = plan_row_level(checks, pred_chunks[0].schema, expr_columns=pred_chunks[0].expr_columns)
     null_mode = filteredRow == "NULL"
     constraints: Dict[str, RowOutcome] = {}
     try:

@@ -54,7 +54,8 @@ def dictionary_columns_to_decode(schema, analyzers: Sequence[Analyzer]) -> set:
     as_plain = [(n, "utf8" if n in dict_cols else dt, nl) for n, dt, nl in schema]
     decode = set()
     for a in analyzers:
-        b = PlanBuilder(as_plain)
+        # (an arithmetic operand reads numeric columns only: collecting leaves them out of b.columns)
+        b = PlanBuilder(as_plain, collect_exprs=True)
         try:
             if isinstance(a, _LengthAnalyzer) or (
                     isinstance(a, (Completeness, ApproxCountDistinct, DataType)) and a.column in dict_cols):
@@ -90,12 +91,12 @@ class ScanPlan:
     requires the compiled kernel (plan creation fails with DQError DQ_E_UNSUPPORTED instead of falling back)."""
 
     def __init__(self, analyzers: Sequence[Analyzer], schema, device: Optional[int] = None, pred_pass: str = "auto",
-                 length_columns: Optional[dict] = None):
+                 length_columns: Optional[dict] = None, expr_columns: Optional[dict] = None):
         import torch
 
         self.analyzers = list(analyzers)
         self.schema = list(schema)
-        b = PlanBuilder(schema, length_columns)
+        b = PlanBuilder(schema, length_columns, expr_columns)
         specs = (L.AnalyzerSpec * max(1, len(self.analyzers)))()
         for i, a in enumerate(self.analyzers):
             op, ca, cb, pr, wr = a._lower(b)
@@ -190,8 +191,9 @@ class ScanPlan:
             pass
 
 
-def _lower_all(analyzers: Sequence[Analyzer], schema, length_columns: Optional[dict] = None):
-    b = PlanBuilder(schema, length_columns)
+def _lower_all(analyzers: Sequence[Analyzer], schema, length_columns: Optional[dict] = None,
+               expr_columns: Optional[dict] = None):
+    b = PlanBuilder(schema, length_columns, expr_columns)
     specs = (L.AnalyzerSpec * max(1, len(analyzers)))()
     for i, a in enumerate(analyzers):
         op, ca, cb, pr, wr = a._lower(b)
@@ -215,11 +217,15 @@ def _explain(b: PlanBuilder, specs, n_specs: int, pred_pass: str):
 
 
 def explain(analyzers: Sequence[Analyzer], schema, pred_pass: str = "auto",
-            length_columns: Optional[dict] = None) -> str:
+            length_columns: Optional[dict] = None, expr_columns: Optional[dict] = None) -> str:
     """The plan dq_plan_create would build for these analyzers, lowered on the host only (dq_plan_explain: no
     GPU): launches per scan, column-pass variants, the predicate program and the generated predicate kernel;
-    an analyzer set over one plan's capacity is shown as the fused plans dq_plan_create splits it into."""
-    b, specs = _lower_all(analyzers, schema, length_columns)
+    an analyzer set over one plan's capacity is shown as the fused plans dq_plan_create splits it into.  Arithmetic
+    operands are shown as the derived columns a run attaches for them (expressions.lowering_schema)."""
+    from .expressions import lowering_schema
+
+    schema, expr_columns = lowering_schema(analyzers, schema, expr_columns)
+    b, specs = _lower_all(analyzers, schema, length_columns, expr_columns)
     rc, text = _explain(b, specs, len(analyzers), pred_pass)
     L.check(rc)
     return text
@@ -227,11 +233,17 @@ def explain(analyzers: Sequence[Analyzer], schema, pred_pass: str = "auto",
 
 def scan_results(data, analyzers: Sequence[Analyzer], pred_pass: str = "auto") -> List[L.State]:
     """Fused scan of all chunks -> raw aggregation-result slot sets, one per analyzer."""
+    from .expressions import attach_for
     from .lengths import attach_length_columns
 
-    # MinLength / MaxLength: their derived length columns, for this run only, before the dictionary routing
-    chunks = _chunks(route_dictionary_columns(attach_length_columns(data, analyzers), analyzers))
-    plan = ScanPlan(analyzers, chunks[0].schema, pred_pass=pred_pass, length_columns=chunks[0].length_columns)
+    # MinLength / MaxLength: their derived length columns, and the derived columns of the predicates' arithmetic
+    # operands, for this run only, before the dictionary routing
+    data, failed, _ = attach_for(attach_length_columns(data, analyzers), analyzers)
+    if failed:
+        raise next(iter(failed.values()))
+    chunks = _chunks(route_dictionary_columns(data, analyzers))
+    plan = ScanPlan(analyzers, chunks[0].schema, pred_pass=pred_pass, length_columns=chunks[0].length_columns,
+                    expr_columns=chunks[0].expr_columns)
     try:
         for t in chunks:
             plan.scan(t)
@@ -245,15 +257,21 @@ def scan_states(data, analyzers: Sequence[Analyzer], pred_pass: str = "auto") ->
     return {a: a._from_result(r) for a, r in zip(analyzers, res)}
 
 
-def gpu_eligible(analyzer: Analyzer, schema, length_columns: Optional[dict] = None) -> Optional[Exception]:
+def gpu_eligible(analyzer: Analyzer, schema, length_columns: Optional[dict] = None,
+                 expr_columns: Optional[dict] = None) -> Optional[Exception]:
     """None if the analyzer lowers into a GPU plan; else the reason (-> fallback set).
 
     Two checks, both on the host: the predicate compiler (SQL text outside the GPU grammar), then the planner
     on this analyzer alone (dq_plan_explain: e.g. a predicate nested deeper than the device stack).  Capacity
     limits of a plan are never a routing reason: dq_plan_create splits a set over them into several fused
-    plans, so only what does not fit a plan by itself goes to the fallback."""
+    plans, so only what does not fit a plan by itself goes to the fallback.  A predicate with arithmetic operands
+    is judged with the derived columns a run attaches for them (those of expr_columns, or as
+    expressions.lowering_schema names them for data that carries none yet)."""
+    from .expressions import lowering_schema
+
     try:
-        b, specs = _lower_all([analyzer], schema, length_columns)
+        schema, expr_columns = lowering_schema([analyzer], schema, expr_columns)
+        b, specs = _lower_all([analyzer], schema, length_columns, expr_columns)
     except UnsupportedPredicate as e:
         return e
     except Exception:
@@ -352,6 +370,16 @@ class AnalysisRunner:
             except Exception as e:  # the derived expression failed: its analyzers fail, the others run
                 failures.update({a: a.toFailureMetric(e) for a in _length_analyzers(passed)})
                 passed = [a for a in passed if a not in failures]
+        # the derived columns of the arithmetic operands in the predicates and `where`s of the analyzers that passed:
+        # one per distinct expression, evaluated once per chunk; a failure fails the analyzers that use it alone
+        from .expressions import attach_for
+
+        data, failed_exprs, per = attach_for(data, passed)
+        for a, used in zip(passed, per):
+            bad = [t for t in used if t in failed_exprs]
+            if bad:
+                failures[a] = a.toFailureMetric(failed_exprs[bad[0]])
+        passed = [a for a in passed if a not in failures]
         data = route_dictionary_columns(data, all_analyzers)  # (a decoded column is a StringType column too)
         grouping = [a for a in passed if getattr(a, "grouping", False)]
         scanning = [a for a in passed if not getattr(a, "grouping", False)]
@@ -400,13 +428,15 @@ class AnalysisRunner:
                              saveStatesWith=None) -> AnalyzerContext:
         if not analyzers:
             return AnalyzerContext.empty()
+        from .expressions import expr_columns_of
         from .lengths import length_columns_of
 
         schema = data_schema(data)
         lengths = length_columns_of(data)
+        exprs = expr_columns_of(data)
         gpu, fallback = [], {}
         for a in analyzers:
-            reason = gpu_eligible(a, schema, lengths)
+            reason = gpu_eligible(a, schema, lengths, exprs)
             if reason is None:
                 gpu.append(a)
             else:

@@ -193,6 +193,7 @@ def plain_utf8(data, columns: Optional[Iterable[str]] = None):
             return t
         out = Table([decoded(c) if c.name in hit else c for c in t.columns.values()])
         out.length_columns = dict(t.length_columns)
+        out.expr_columns = dict(t.expr_columns)
         return out
 
     return one(data) if isinstance(data, Table) else [one(t) for t in data]
@@ -213,6 +214,8 @@ class Table:
         self.num_rows = n or 0
         # source string column -> its derived length column, for tables lengths.attach_length_columns built
         self.length_columns: Dict[str, str] = {}
+        # canonical arithmetic expression -> its derived column, for tables expressions.attach_expression_columns built
+        self.expr_columns: Dict[str, str] = {}
 
     @property
     def schema(self) -> List[Tuple[str, str, bool]]:

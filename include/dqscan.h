@@ -43,7 +43,8 @@ extern "C" {
                                 so are dq_freq_materialize / _self_contained / _to_bytes / _from_bytes / _take_values /
                                 _mutual_information (self-contained frequency tables) and the row-level results:
                                 dq_row_program_* / dq_row_outcomes (per-row predicate outcomes as bitmaps),
-                                dq_freq_unique_rows (the rows whose group has count 1) */
+                                dq_freq_unique_rows (the rows whose group has count 1); arithmetic operands of
+                                predicates: DQ_PRED_EXPR, dq_pred_pool_num_exprs / _expr, dq_expr_eval / _host */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -142,9 +143,13 @@ enum dq_pred_kind {
   DQ_PRED_IS_NULL = 11,    /* a IS NULL */
   DQ_PRED_IS_NOT_NULL = 12,/* a IS NOT NULL */
   DQ_PRED_COALESCE = 13,   /* COALESCE(a, b): a = COLUMN node, b = literal node */
-  DQ_PRED_REGEX = 14       /* regex over a UTF8 column: a = COLUMN node, i64 = index into the plan's
+  DQ_PRED_REGEX = 14,      /* regex over a UTF8 column: a = COLUMN node, i64 = index into the plan's
                               patterns (dq_plan_create_ex), cmp = enum dq_regex_mode;
                               string equality / IN lists lower to mode DQ_REGEX_FULL */
+  DQ_PRED_EXPR = 15        /* an arithmetic operand (dq_pred_pool_add only): a = index into the pool's expression
+                              list (dq_pred_pool_expr), cmp = its result type (enum dq_type).  A plan never sees
+                              this kind: the caller materialises the expression as a derived column (dq_expr_eval)
+                              and hands the node over as DQ_PRED_COLUMN of that column */
 };
 /* DQ_PRED_REGEX semantics (java.util.regex Matcher.find on the value's code points):
  *   DQ_REGEX_RLIKE            `col RLIKE p`: NULL on a NULL value, else TRUE iff find() succeeds;
@@ -393,7 +398,8 @@ dq_status dq_regex_match_host(const char* pattern, int32_t mode, const uint8_t* 
  * and accumulates the nodes and regex patterns of every root of one plan, ready for dq_plan_create_ex.
  * Grammar: OR / AND / NOT, comparisons < <= > >= = == != <>, IS [NOT] NULL, COALESCE(a, b), parentheses,
  * numeric literals typed as Spark 2.2 (`3` int, `3.0` exact decimal, `3e0` double), NULL / TRUE / FALSE,
- * string (in)equality and [NOT] IN ('a', ...) on a string column (lowered to a DQ_REGEX_FULL node).
+ * string (in)equality and [NOT] IN ('a', ...) on a string column (lowered to a DQ_REGEX_FULL node), and arithmetic
+ * (+ - * / %, unary minus) on each side of a comparison and under IS [NOT] NULL ("Arithmetic operands" below).
  * dq_pred_pool_add: DQ_E_UNSUPPORTED (reason in dq_last_error) for text outside that grammar -- string
  * ordering, a numeric comparison of a string column, LIKE / RLIKE / BETWEEN, function calls, typed literal
  * suffixes, escapes -- i.e. route the analyzer to the Spark fallback; DQ_E_INVALID "no such column: x" for
@@ -409,6 +415,92 @@ const dq_pred_node* dq_pred_pool_nodes(const dq_pred_pool* pool);
 int32_t dq_pred_pool_num_patterns(const dq_pred_pool* pool);
 const char* const* dq_pred_pool_patterns(const dq_pred_pool* pool);
 void dq_pred_pool_destroy(dq_pred_pool* pool);
+
+/* ---- Arithmetic operands: + - * / % over numeric columns (additions under ABI 6) ----
+ * Each side of a comparison, and the operand of IS [NOT] NULL, is an arithmetic expression:
+ *     operand := sum
+ *     sum     := term ( (+ | -) term )*
+ *     term    := unary ( (* | / | %) unary )*
+ *     unary   := - unary | primary
+ *     primary := column | `column` | number | ( sum ) | the other operands of the grammar above
+ * A primary alone lowers exactly as before, and `- number` stays a literal.  An operand with at least one operator
+ * and at least one column becomes one DQ_PRED_EXPR node whose `a` indexes the pool's expression list; equal canonical
+ * texts (fully parenthesised, columns in backticks) share one entry within a pool.  The caller evaluates every
+ * entry once per chunk with dq_expr_eval into a derived column and passes the node to the plan as DQ_PRED_COLUMN of
+ * that column, so every comparison rule of the plan applies to the result unchanged.
+ *
+ * Semantics (Spark 2.2, non-ANSI):
+ *   types      Byte < Short < Int < Long < Float < Double (I8 < I16 < I32 < I64 < F32 < F64)
+ *   literals   an integer literal is IntegerType if it fits, else LongType; `3e0` is Double; a decimal literal
+ *              (`2.5`) next to a Float or Double operand is cast to Double
+ *   + - * %    both sides are cast to the wider type, which is the result type
+ *   integral   results wrap in two's complement at the result width: Byte 127 + 1 = -128, Int MIN % -1 = 0
+ *   Float      binary32 arithmetic, rounded after each operation; Double: binary64.  No contraction: a * b + c is
+ *              two roundings, never an FMA
+ *   /          both sides are cast to Double (7 / 2 = 3.5); a divisor == 0, of either sign of zero, gives NULL
+ *   %          NULL on a zero divisor; integrals: Java's truncated remainder; Float / Double: Java %, i.e. fmod
+ *   unary -    keeps the type and wraps
+ *   NULL       any NULL operand gives NULL
+ *   result     a column of the result type (I8 I16 I32 I64 F32 F64), nullable whenever an input is or when the
+ *              program contains / or %
+ * DQ_E_UNSUPPORTED, each with the reason in dq_last_error: a non-numeric operand (bool, date, timestamp, string),
+ * a decimal(p,s) column inside arithmetic, a decimal literal combined with an integral operand or another decimal
+ * literal (decimal arithmetic), COALESCE or NULL inside arithmetic, an operator expression without a column,
+ * function calls, BETWEEN, IN over numbers or over an expression, an expression used as a boolean, and a program
+ * beyond the limits below.
+ *
+ * A program is postfix over a value stack.  Every instruction carries the type it produces: COL pushes column
+ * `arg` of the program's column list (type = the column's), LIT pushes literal `arg` (I32 / I64 / F64), CAST widens
+ * the top of the stack to `type`, NEG negates it at `type`; ADD SUB MUL MOD pop b then a, both of `type`, and push
+ * a op b; DIV the same with `type` = F64.  The compiler emits every cast, so an evaluator needs no type rules. */
+#define DQ_EXPR_MAX_COLUMNS 8   /* distinct source columns of one expression */
+#define DQ_EXPR_MAX_INSTRS 32   /* program length */
+#define DQ_EXPR_MAX_LITERALS 16 /* literals of one program (the program length binds first) */
+#define DQ_EXPR_MAX_STACK 8     /* value-stack depth (the kernel holds the stack in registers) */
+enum dq_expr_op {
+  DQ_EXPR_COL = 1, DQ_EXPR_LIT = 2, DQ_EXPR_CAST = 3, DQ_EXPR_NEG = 4,
+  DQ_EXPR_ADD = 5, DQ_EXPR_SUB = 6, DQ_EXPR_MUL = 7, DQ_EXPR_DIV = 8, DQ_EXPR_MOD = 9
+};
+typedef struct dq_expr_instr {
+  int32_t op;   /* enum dq_expr_op */
+  int32_t arg;  /* COL: index into columns[]; LIT: index into literals[]; else 0 */
+  int32_t type; /* enum dq_type of the value the instruction leaves on the stack */
+  int32_t reserved;
+} dq_expr_instr;
+typedef struct dq_expr_literal {
+  int32_t type; /* DQ_TYPE_I32 / DQ_TYPE_I64: i64; DQ_TYPE_F64: f64 */
+  int32_t reserved;
+  int64_t i64;
+  double f64;
+} dq_expr_literal;
+typedef struct dq_expr_program {
+  int32_t n_instrs, n_columns, n_literals;
+  int32_t result_type;  /* enum dq_type: I8 I16 I32 I64 F32 F64 */
+  int32_t stack_depth;  /* the deepest the value stack gets */
+  int32_t divides;      /* 1: the program holds / or %, so the result is nullable whatever the inputs are */
+  dq_expr_instr instrs[DQ_EXPR_MAX_INSTRS];
+  int32_t columns[DQ_EXPR_MAX_COLUMNS];      /* positions in the pool's column list, in first-use order */
+  int32_t column_types[DQ_EXPR_MAX_COLUMNS]; /* their enum dq_type */
+  dq_expr_literal literals[DQ_EXPR_MAX_LITERALS];
+  const char* text;     /* canonical text; the pool's (dq_pred_pool_expr), unused by dq_expr_eval */
+} dq_expr_program;
+/* The expressions the pool's DQ_PRED_EXPR nodes refer to; a program stays valid until the pool is destroyed. */
+int32_t dq_pred_pool_num_exprs(const dq_pred_pool* pool);
+const dq_expr_program* dq_pred_pool_expr(const dq_pred_pool* pool, int32_t index);
+/* Evaluate one program over n_rows rows into a derived column.  cols: prog->n_columns views, in the order of
+ * prog->columns, of the fixed-width types prog->column_types names (values 16-byte aligned, n_rows elements;
+ * validity NULL: no NULL row; offsets unused, reserved 0).  out_values: n_rows elements of the result type (16-byte
+ * aligned); out_validity: ceil(n_rows / 64) 64-bit words (8-byte aligned; bits past n_rows are written 0); both
+ * device, caller-allocated; every value and every word of the n_rows rows is written (a NULL row's value is 0),
+ * nothing beyond them.  *nulls_out (host) = the NULL rows; the call synchronises hip_stream.  n_rows = 0: DQ_OK,
+ * nothing written.  The program is checked first (limits, indices, the stack discipline and the type of every
+ * operand): a malformed one, a NULL or misaligned buffer, n_rows < 0 or reserved != 0 are DQ_E_INVALID, a column
+ * or result type outside the six numeric ones is DQ_E_UNSUPPORTED, and nothing is launched. */
+dq_status dq_expr_eval(const dq_expr_program* prog, const dq_column_view* cols, int64_t n_rows, void* out_values,
+                       uint64_t* out_validity, int32_t device, void* hip_stream, int64_t* nulls_out);
+/* The same evaluation on the CPU, no device (tests of the compiler and of the rules): cols[k] = host pointers. */
+dq_status dq_expr_eval_host(const dq_expr_program* prog, const dq_column_view* cols, int64_t n_rows, void* out_values,
+                            uint64_t* out_validity, int64_t* nulls_out);
 /* Launch on this hipStream_t from now on (NULL = the device null stream).  A new plan launches on its
    own non-blocking stream, which does not order against other streams: set the producer's stream. */
 dq_status dq_plan_set_stream(dq_plan* plan, void* hip_stream);
