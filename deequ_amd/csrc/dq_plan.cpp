@@ -25,17 +25,11 @@
 #include <tuple>
 #include <vector>
 
-#include "dq_device.h"
-#include "dq_hip_host.h"
+#include "dq_plan_host.h"
 #include "dq_pred_jit.h"
+#include "dq_pred_lower.h"
 
-// predicate-pass workgroups per chunk (A/B builds: -DDQ_PRED_WGS=...)
-// rows per range at least this many: below it a launch's time goes to dispatching workgroups and to their
-// fixed work (shift search, reductions, partial records), not to the rows -- a 10 M-row chunk (C1) otherwise
-// ran 4-12 K workgroups of 2-4 K rows; every chunk of >= 16 K x 8192 rows is unaffected
-#ifndef DQ_MIN_RANGE_ROWS
-#define DQ_MIN_RANGE_ROWS 16384
-#endif
+// (DQ_MIN_RANGE_ROWS, the column passes' floor too, and DQ_PRED_WGS: dq_plan_host.h)
 // the validity-only pass (Completeness of a column): 8 KB of bitmap per 64 K rows, so its floor is higher (C1,
 // 10 M rows: validity 21 -> 9-11 us, i64 moments 41 -> 31 us, finalize 13 -> 9 us; 256 K measured the same,
 // profiles/r5_ab.txt r5i / r5j)
@@ -48,37 +42,8 @@
 #ifndef DQ_PAIR_ONE_ROUND
 #define DQ_PAIR_ONE_ROUND 1  // Correlation pass sized to one resident round (0: the column passes' ranges; A/B builds)
 #endif
-#ifndef DQ_PRED_WGS
-#define DQ_PRED_WGS 2048
-#endif
-#include "dq_regex.h"
 
 namespace dq {
-
-hipError_t launch_pred_scan(const PredProgram* prog, const ScanCols& cols, const ScanBitmaps& bm, int64_t n_rows,
-                            int64_t rows_per_range, int32_t nranges, PredPartial* acc, int32_t lds_bytes, hipStream_t st,
-                            bool has_regex);
-hipError_t launch_row_outcomes(const PredProgram* prog, const ScanCols& cols, uint32_t* const* pass,
-                               uint32_t* const* applies, int32_t n_out, int64_t n_rows, int64_t rows_per_range,
-                               int32_t nranges, PredPartial* acc, int32_t lds_bytes, hipStream_t st, bool has_regex);
-hipError_t launch_column_scan(int32_t variant, const ColTask* tasks, int32_t ntasks, int32_t part_base,
-                              const ScanCols& cols, const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range,
-                              int32_t nranges, ColPartial* partials, uint32_t* hll_acc, const uint32_t* hll_floor,
-                              bool long_str, hipStream_t st);
-hipError_t launch_pair_scan(const PairWG* wgs, int32_t nwg, const ScanCols& cols, const ScanBitmaps& bm,
-                            const uint32_t* ones, int64_t n_rows, int64_t rows_per_range, int32_t nranges,
-                            CorrPartial* pair_part, ColPartial* col_part, int32_t* redo, bool all_f64, bool ring,
-                            bool minmax, hipStream_t st);
-hipError_t pair_scan_residency(bool all_f64, bool ring, bool minmax, int32_t* per_cu);
-hipError_t launch_finalize(int32_t ncol, int32_t nranges_col, const ColPartial* col_part, ColPartial* col_acc,
-                           int32_t npair, int32_t nranges_pair, const CorrPartial* pair_part, CorrPartial* pair_acc,
-                           int32_t has_pred, int32_t nranges_pred, const PredPartial* pred_part, PredPartial* pred_acc, const FinRanges& fr, int64_t* rare_dev, int64_t* rare_host,
-                           int32_t nhll, const uint32_t* hll_acc, uint32_t* hll_floor, hipStream_t st);
-hipError_t launch_dict_scan(const ColTask* tasks, int32_t ntasks, int32_t part_base, const ScanCols& cols,
-                            const DictSizes& sizes, const ScanBitmaps& bm, int64_t n_rows, int64_t rows_per_range,
-                            int32_t nranges, ColPartial* partials, uint32_t* hll_acc, hipStream_t stream);
-hipError_t launch_init_acc(ColPartial* col_acc, int32_t ncol, CorrPartial* pair_acc, int32_t npair, int64_t* rare_dev,
-                           hipStream_t st);
 
 static thread_local char g_err[1024] = "";
 // set with the error when a plan exceeds a fixed per-plan capacity (columns, predicates, counters, `where`
@@ -103,31 +68,6 @@ static dq_status cap_error(const char* fmt, ...) {
   return DQ_E_UNSUPPORTED;
 }
 
-// Preconditions.isNumeric (Analyzer.scala:322-334): ByteType .. DoubleType and DecimalType
-static bool is_numeric(int32_t t) {
-  return t == DQ_TYPE_F64 || t == DQ_TYPE_I64 || t == DQ_TYPE_I32 || t == DQ_TYPE_F32 || t == DQ_TYPE_I16 ||
-         t == DQ_TYPE_I8 || is_decimal(t);
-}
-static bool is_integral(int32_t t) { return t == DQ_TYPE_I64 || t == DQ_TYPE_I32 || t == DQ_TYPE_I16 || t == DQ_TYPE_I8; }
-static bool is_floating(int32_t t) { return t == DQ_TYPE_F64 || t == DQ_TYPE_F32; }
-static bool is_string(int32_t t) { return t == DQ_TYPE_UTF8 || t == DQ_TYPE_LARGE_UTF8; }
-static bool is_dict(int32_t t) { return t == DQ_TYPE_DICT_UTF8; }
-// the column types a plan takes: type_valid's, and a dictionary-encoded string column
-static bool plan_type_valid(int32_t t) { return type_valid(t) || is_dict(t); }
-static int32_t kind_of(int32_t t) {
-  switch (t) {
-    case DQ_TYPE_F64: return CK_F64;
-    case DQ_TYPE_I64: case DQ_TYPE_TIMESTAMP: return CK_I64;
-    case DQ_TYPE_I32: case DQ_TYPE_DATE32: case DQ_TYPE_DICT_UTF8: return CK_I32;  // (a dictionary column's indices)
-    case DQ_TYPE_F32: return CK_F32;
-    case DQ_TYPE_I16: return CK_I16;
-    case DQ_TYPE_I8: return CK_I8;
-    case DQ_TYPE_BOOL: return CK_BOOL;
-    case DQ_TYPE_UTF8: return CK_UTF8;
-    case DQ_TYPE_LARGE_UTF8: return CK_LUTF8;
-    default: return CK_D128;  // (type_valid: a DECIMAL128 code)
-  }
-}
 // the Correlation pass's kind of a column: its ColKind, for a decimal CK_D128 | scale << 8 | (precision <= 18) << 16
 // (dq_pair.hip casts it to double as it loads it)
 static int32_t pair_kind(int32_t t) {
@@ -144,8 +84,6 @@ static int64_t value_bytes_x1000(int32_t t) {
     default: return is_decimal(t) ? 16000 : 8000;
   }
 }
-// (double)(float)v as Java's long -> float conversion rounds it (to nearest, ties to even)
-static double int_as_float(int64_t v) { return (double)(float)v; }
 
 // Where one analyzer's aggregation-result slots come from.
 struct SpecOut {
@@ -157,487 +95,6 @@ struct SpecOut {
   int32_t col_type = 0;
   bool has_where = false;
 };
-
-// ------------------------------------------------------------------------------------------
-// Predicate lowering: IR tree -> postfix program over three-valued atoms
-// ------------------------------------------------------------------------------------------
-struct Lit {  // exact literal: int / decimal (unscaled, scale) / double / null / bool
-  enum K { INT, DEC, DBL, NUL, BOOL } k;
-  int64_t i = 0;
-  int32_t scale = 0;
-  double d = 0.0;
-};
-
-static double lit_to_double(const Lit& l) {
-  if (l.k == Lit::DBL) return l.d;
-  if (l.k == Lit::INT || l.k == Lit::BOOL) return (double)l.i;
-  // decimal -> correctly rounded double via its decimal text (Decimal.toDouble)
-  char buf[64];
-  long long u = (long long)l.i;
-  bool neg = u < 0;
-  unsigned long long a = neg ? (unsigned long long)(-(u + 1)) + 1ull : (unsigned long long)u;
-  std::string digits = std::to_string(a);
-  while ((int)digits.size() <= l.scale) digits = "0" + digits;
-  std::string txt = (neg ? "-" : "") + digits.substr(0, digits.size() - l.scale) +
-                    (l.scale ? "." + digits.substr(digits.size() - l.scale) : "");
-  std::snprintf(buf, sizeof(buf), "%s", txt.c_str());
-  return std::strtod(buf, nullptr);
-}
-
-static bool pow10_i64(int s, int64_t& out) {
-  if (s < 0 || s > 18) return false;
-  int64_t p = 1;
-  for (int i = 0; i < s; ++i) p *= 10;
-  out = p;
-  return true;
-}
-
-// floor(u / p) for p > 0, without the overflow of -u + p - 1 near INT64_MIN
-static int64_t floor_div(int64_t u, int64_t p) {
-  const int64_t q = u / p;
-  return (u % p != 0 && u < 0) ? q - 1 : q;
-}
-
-// exact compare of two non-double literals: returns -1/0/1
-static int exact_cmp(const Lit& a, const Lit& b) {
-  int64_t pa = 1, pb = 1;
-  pow10_i64(a.k == Lit::DEC ? a.scale : 0, pa);
-  pow10_i64(b.k == Lit::DEC ? b.scale : 0, pb);
-  __int128 x = (__int128)a.i * pb, y = (__int128)b.i * pa;
-  return (x > y) - (x < y);
-}
-
-static int flip_cmp(int c) {
-  switch (c) {
-    case DQ_CMP_LT: return DQ_CMP_GT;
-    case DQ_CMP_LE: return DQ_CMP_GE;
-    case DQ_CMP_GT: return DQ_CMP_LT;
-    case DQ_CMP_GE: return DQ_CMP_LE;
-    default: return c;
-  }
-}
-
-static bool cmp_holds(int c, int r) {
-  switch (c) {
-    case DQ_CMP_LT: return r < 0;
-    case DQ_CMP_LE: return r <= 0;
-    case DQ_CMP_GT: return r > 0;
-    case DQ_CMP_GE: return r >= 0;
-    case DQ_CMP_EQ: return r == 0;
-    default: return r != 0;
-  }
-}
-
-static int dbl_cmp(double a, double b) {  // Spark nanSafeCompare
-  bool an = a != a, bn = b != b;
-  if (an || bn) return (an && bn) ? 0 : (an ? 1 : -1);
-  return (a > b) - (a < b);
-}
-
-// literal-vs-literal comparison under Spark coercion: any double -> double, else exact decimal
-static int lit_cmp_result(int cmp, const Lit& a, const Lit& b) {  // returns NR_*
-  if (a.k == Lit::NUL || b.k == Lit::NUL) return NR_NULL;
-  int r = (a.k == Lit::DBL || b.k == Lit::DBL) ? dbl_cmp(lit_to_double(a), lit_to_double(b)) : exact_cmp(a, b);
-  return cmp_holds(cmp, r) ? NR_TRUE : NR_FALSE;
-}
-
-static int to_cmpop(int c) {
-  switch (c) {
-    case DQ_CMP_LT: return C_LT;
-    case DQ_CMP_LE: return C_LE;
-    case DQ_CMP_GT: return C_GT;
-    case DQ_CMP_GE: return C_GE;
-    case DQ_CMP_EQ: return C_EQ;
-    default: return C_NE;
-  }
-}
-
-struct Lowering {
-  const dq_pred_node* pool;
-  int32_t n_pred;
-  const std::vector<dq_column_desc>* schema;
-  std::vector<PredInstr> out;
-  const std::vector<std::string>* patterns = nullptr;
-  std::vector<uint16_t>* regex_blob = nullptr;              // concatenated DFAs (dq_regex.h layout)
-  std::map<std::pair<int64_t, int32_t>, int64_t> regex_at;  // (pattern, mode) -> blob word offset
-
-  dq_status lit_of(int32_t idx, Lit& l) {
-    const dq_pred_node& n = pool[idx];
-    switch (n.kind) {
-      case DQ_PRED_LIT_INT: l.k = Lit::INT; l.i = n.i64; return DQ_OK;
-      case DQ_PRED_LIT_DECIMAL:
-        if (n.cmp < 0 || n.cmp > 18) return set_error(DQ_E_UNSUPPORTED, "decimal literal scale %d unsupported", n.cmp);
-        l.k = Lit::DEC; l.i = n.i64; l.scale = n.cmp; return DQ_OK;
-      case DQ_PRED_LIT_DOUBLE: l.k = Lit::DBL; l.d = n.f64; return DQ_OK;
-      case DQ_PRED_LIT_NULL: l.k = Lit::NUL; return DQ_OK;
-      case DQ_PRED_LIT_BOOL: l.k = Lit::BOOL; l.i = n.i64 ? 1 : 0; return DQ_OK;
-      default: return set_error(DQ_E_UNSUPPORTED, "node %d is not a literal", idx);
-    }
-  }
-  bool is_lit(int32_t idx) const {
-    int k = pool[idx].kind;
-    return k >= DQ_PRED_LIT_INT && k <= DQ_PRED_LIT_BOOL;
-  }
-  dq_status check_idx(int32_t idx) {
-    if (idx < 0 || idx >= n_pred) return set_error(DQ_E_INVALID, "predicate node index %d out of range", idx);
-    return DQ_OK;
-  }
-  dq_status check_col(int32_t c) {
-    if (c < 0 || c >= (int32_t)schema->size()) return set_error(DQ_E_INVALID, "predicate column %d out of range", c);
-    if (is_dict((*schema)[c].type))  // (every atom's column passes here)
-      return set_error(DQ_E_UNSUPPORTED, "predicate over dictionary-encoded column %d: decode it (dq_dict_decode)", c);
-    return DQ_OK;
-  }
-  void push_const(int nr) {
-    PredInstr p{};
-    p.op = PO_CONST; p.null_res = nr; p.col_a = -1; p.col_b = -1;
-    out.push_back(p);
-  }
-
-  // operand = column, or COALESCE(column, literal)
-  struct Operand { int32_t col = -1; bool has_fallback = false; Lit fallback{}; };
-
-  dq_status operand_of(int32_t idx, Operand& o) {
-    const dq_pred_node& n = pool[idx];
-    if (n.kind == DQ_PRED_COLUMN) {
-      if (dq_status s = check_col(n.a)) return s;
-      o.col = n.a;
-      return DQ_OK;
-    }
-    if (n.kind == DQ_PRED_COALESCE) {
-      if (dq_status s = check_idx(n.a)) return s;
-      if (dq_status s = check_idx(n.b)) return s;
-      if (pool[n.a].kind != DQ_PRED_COLUMN || !is_lit(n.b))
-        return set_error(DQ_E_UNSUPPORTED, "COALESCE supported only as COALESCE(column, literal)");
-      if (dq_status s = check_col(pool[n.a].a)) return s;
-      o.col = pool[n.a].a;
-      o.has_fallback = true;
-      return lit_of(n.b, o.fallback);
-    }
-    return set_error(DQ_E_UNSUPPORTED, "unsupported comparison operand (node kind %d)", n.kind);
-  }
-
-  // DecimalType(p, s) column CMP an integer / decimal literal.  Spark 2.2 (DecimalPrecision) casts an integer
-  // literal to DecimalType(10, 0) (an int) or (20, 0) (a long) and both sides to the wider decimal type
-  // (max of the integer digits + max of the scales); while that fits 38 digits every cast is exact, so the
-  // comparison is the exact rational one, rewritten here into a bound B on the unscaled value u: u CMP B.  Wider
-  // types (Spark bounds them to 38 digits and can turn values NULL), double literals (the decimal is cast to
-  // double) and boolean literals stay on the fallback.  Precision <= 18: one atom on the low word (the whole value,
-  // |u| < 10^18); wider: the 128-bit comparison as atoms on the high word H and the low word L (compared unsigned),
-  // e.g. u < B  <=>  H < Bh OR (H = Bh AND L <u Bl).
-  dq_status emit_dec_lit(const Operand& o, int cmp, const Lit& lit, int32_t type) {
-    const int prec = DQ_DECIMAL_PRECISION(type), sc = DQ_DECIMAL_SCALE(type);
-    auto fits = [&](const Lit& l) {  // the wider decimal type of the column and the literal fits 38 digits
-      if (l.k == Lit::NUL) return true;
-      if (l.k != Lit::INT && l.k != Lit::DEC) return false;
-      const int ls = l.k == Lit::DEC ? l.scale : 0;
-      int lp;
-      if (l.k == Lit::INT) lp = (l.i >= INT32_MIN && l.i <= INT32_MAX) ? 10 : 20;
-      else {
-        const uint64_t a = l.i < 0 ? (uint64_t)0 - (uint64_t)l.i : (uint64_t)l.i;
-        lp = std::max((int)std::to_string(a).size(), ls);
-      }
-      return std::max(prec - sc, lp - ls) + std::max(sc, ls) <= kDecMaxPrecision;
-    };
-    if (!fits(lit) || (o.has_fallback && !fits(o.fallback)))
-      return set_error(DQ_E_UNSUPPORTED, "decimal column %d compared with a %s literal", o.col,
-                       lit.k == Lit::DBL || o.fallback.k == Lit::DBL ? "double" : "wider or boolean");
-    const int nr = o.has_fallback ? lit_cmp_result(cmp, o.fallback, lit) : NR_NULL;
-    if (lit.k == Lit::NUL) { push_const(NR_NULL); return DQ_OK; }
-    // u / 10^sc CMP L / 10^t  ->  u CMP' B
-    const int t = lit.k == Lit::DEC ? lit.scale : 0;
-    int c2;
-    i128 B;
-    if (t <= sc) {
-      i128 m = 1;
-      for (int k = 0; k < sc - t; ++k) m *= 10;
-      B = (i128)lit.i * m;  // (fits: the wider type has at most 38 digits)
-      c2 = to_cmpop(cmp);
-    } else {
-      int64_t p10;
-      pow10_i64(t - sc, p10);
-      const int64_t u = lit.i;
-      const int64_t fl = floor_div(u, p10);
-      const bool exact = (u % p10) == 0;
-      const int64_t ce = exact ? fl : fl + 1;
-      switch (cmp) {
-        case DQ_CMP_LT: c2 = C_LT; B = ce; break;
-        case DQ_CMP_LE: c2 = C_LE; B = fl; break;
-        case DQ_CMP_GT: c2 = C_GT; B = fl; break;
-        case DQ_CMP_GE: c2 = C_GE; B = ce; break;
-        case DQ_CMP_EQ: c2 = exact ? C_EQ : C_FALSE; B = fl; break;
-        default: c2 = exact ? C_NE : C_TRUE; B = fl; break;
-      }
-    }
-    auto atom = [&](int kind, int c, int64_t v) {
-      PredInstr p{};
-      p.op = PO_ATOM_CMP; p.col_a = o.col; p.col_b = -1; p.kind_a = kind; p.kind_b = 0;
-      p.ctype = CT_INT; p.cmp = c; p.lit_i = v; p.null_res = nr;
-      out.push_back(p);
-    };
-    auto logic = [&](int op) {
-      PredInstr p{};
-      p.op = op; p.col_a = p.col_b = -1;
-      out.push_back(p);
-    };
-    if (c2 == C_TRUE || c2 == C_FALSE) { atom(CK_D128_LO, c2, 0); return DQ_OK; }
-    if (prec <= 18) {
-      if (B > (i128)INT64_MAX || B < (i128)INT64_MIN) {  // every |u| < 10^18 lies on one side of B
-        const bool below = B > 0;  // u < B for every u
-        const bool holds = c2 == C_LT || c2 == C_LE || c2 == C_NE ? below : (c2 == C_EQ ? false : !below);
-        atom(CK_D128_LO, holds ? C_TRUE : C_FALSE, 0);
-      } else {
-        atom(CK_D128_LO, c2, (int64_t)B);
-      }
-      return DQ_OK;
-    }
-    const int64_t bh = (int64_t)(B >> 64);
-    const int64_t bl = (int64_t)((uint64_t)B ^ (1ull << 63));  // (CK_D128_LOU flips the loaded low word the same way)
-    if (c2 == C_EQ || c2 == C_NE) {
-      atom(CK_D128_HI, c2, bh);
-      atom(CK_D128_LOU, c2, bl);
-      logic(c2 == C_EQ ? PO_AND : PO_OR);
-      return DQ_OK;
-    }
-    const bool lt = c2 == C_LT || c2 == C_LE;
-    atom(CK_D128_HI, lt ? C_LT : C_GT, bh);
-    atom(CK_D128_HI, C_EQ, bh);
-    atom(CK_D128_LOU, c2, bl);
-    logic(PO_AND);
-    logic(PO_OR);
-    return DQ_OK;
-  }
-
-  // column CMP literal, or COALESCE(column, fallback) CMP literal, with Spark 2.2's coercions.  The operand's type
-  // comes first: the column's, widened by the fallback (COALESCE takes the common type of its arguments); then
-  // the comparison's type from the operand and the literal:
-  //   integral operand (integral column, fallback NULL / integer / decimal): vs an integer or decimal literal
-  //     exact, vs a double literal in double;
-  //   an integral column with a double fallback is a DoubleType operand: every literal is cast to double and the
-  //     column compares as (double)value, also against an integer or decimal literal;
-  //   FloatType operand (float column, fallback NULL / integer, the integer cast to float): vs an integer literal
-  //     in float (the literal rounded to float: findTightestCommonType), vs a decimal literal of any scale or a
-  //     double literal in double (DecimalPrecision: the decimal cast to double);
-  //   a float column with a decimal or double fallback is a DoubleType operand: every literal is cast to double, an
-  //     integer one too (not rounded to float);
-  //   DoubleType column: the fallback and the literal cast to double.
-  // A float widens to double exactly, so every float case is a double compare with the literal rounded as above.
-  // null_res is the comparison of the fallback, widened the same way, with the literal.
-  dq_status emit_col_lit(const Operand& o, int cmp, Lit lit) {
-    const dq_column_desc& cd = (*schema)[o.col];
-    if (is_decimal(cd.type)) return emit_dec_lit(o, cmp, lit, cd.type);
-    const bool boolean = cd.type == DQ_TYPE_BOOL;
-    if (!is_numeric(cd.type) && !boolean)
-      return set_error(DQ_E_UNSUPPORTED, "comparison on a non-numeric column (%d)", o.col);
-    PredInstr p{};
-    p.op = PO_ATOM_CMP; p.col_a = o.col; p.col_b = -1; p.kind_a = kind_of(cd.type); p.kind_b = 0;
-    Lit fb = o.fallback;
-    if (boolean) {
-      // BooleanType vs a boolean literal (Spark orders false < true); against a number Spark 2.2 rewrites
-      // (BooleanEquality) or casts -- not restated here: the fallback
-      if ((lit.k != Lit::BOOL && lit.k != Lit::NUL) || (o.has_fallback && fb.k != Lit::BOOL && fb.k != Lit::NUL))
-        return set_error(DQ_E_UNSUPPORTED, "boolean column compared with a non-boolean literal");
-      if (lit.k == Lit::BOOL) lit.k = Lit::INT;
-      if (fb.k == Lit::BOOL) fb.k = Lit::INT;
-    } else {
-      const bool fb_wide = o.has_fallback && (fb.k == Lit::DBL || (fb.k == Lit::DEC && cd.type == DQ_TYPE_F32));
-      const bool dbl_operand = cd.type == DQ_TYPE_F64 || fb_wide;
-      auto widen = [](Lit& l, bool in_float) {  // an integer or decimal literal as the double it compares as
-        if (l.k != Lit::INT && l.k != Lit::DEC) return;
-        l.d = in_float && l.k == Lit::INT ? int_as_float(l.i) : lit_to_double(l);
-        l.k = Lit::DBL;
-      };
-      if (is_floating(cd.type) || dbl_operand) {
-        if (o.has_fallback) widen(fb, cd.type == DQ_TYPE_F32);
-        widen(lit, cd.type == DQ_TYPE_F32 && !dbl_operand);
-      }
-    }
-    p.null_res = o.has_fallback ? lit_cmp_result(cmp, fb, lit) : NR_NULL;
-    if (lit.k == Lit::NUL) { push_const(NR_NULL); return DQ_OK; }
-    if (lit.k == Lit::BOOL) return set_error(DQ_E_UNSUPPORTED, "boolean literal compared with a number");
-    if (is_floating(cd.type) || lit.k == Lit::DBL) {
-      p.ctype = CT_DBL; p.cmp = to_cmpop(cmp); p.lit_d = lit_to_double(lit);
-    } else if (lit.k == Lit::INT || (lit.k == Lit::DEC && lit.scale == 0)) {
-      p.ctype = CT_INT; p.cmp = to_cmpop(cmp); p.lit_i = lit.i;
-    } else {
-      // integral column vs decimal literal v = u / 10^s: exact rewrite to integer bounds
-      int64_t p10;
-      pow10_i64(lit.scale, p10);
-      int64_t u = lit.i;
-      int64_t fl = floor_div(u, p10);
-      bool integral = (u % p10) == 0;
-      int64_t ce = integral ? fl : fl + 1;                      // ceil
-      p.ctype = CT_INT;
-      switch (cmp) {
-        case DQ_CMP_LT: p.cmp = C_LT; p.lit_i = ce; break;      // x < v  <=> x < ceil(v)
-        case DQ_CMP_LE: p.cmp = C_LE; p.lit_i = fl; break;      // x <= v <=> x <= floor(v)
-        case DQ_CMP_GT: p.cmp = C_GT; p.lit_i = fl; break;      // x > v  <=> x > floor(v)
-        case DQ_CMP_GE: p.cmp = C_GE; p.lit_i = ce; break;      // x >= v <=> x >= ceil(v)
-        case DQ_CMP_EQ: p.cmp = integral ? C_EQ : C_FALSE; p.lit_i = fl; break;
-        default: p.cmp = integral ? C_NE : C_TRUE; p.lit_i = fl; break;
-      }
-    }
-    out.push_back(p);
-    return DQ_OK;
-  }
-
-  dq_status lower(int32_t idx, int depth) {
-    if (dq_status s = check_idx(idx)) return s;
-    if (depth > 30) return set_error(DQ_E_UNSUPPORTED, "predicate nesting too deep");
-    const dq_pred_node& n = pool[idx];
-    switch (n.kind) {
-      case DQ_PRED_AND:
-      case DQ_PRED_OR: {
-        if (dq_status s = lower(n.a, depth + 1)) return s;
-        if (dq_status s = lower(n.b, depth + 1)) return s;
-        PredInstr p{};
-        p.op = n.kind == DQ_PRED_AND ? PO_AND : PO_OR; p.col_a = p.col_b = -1;
-        out.push_back(p);
-        return DQ_OK;
-      }
-      case DQ_PRED_NOT: {
-        if (dq_status s = lower(n.a, depth + 1)) return s;
-        PredInstr p{};
-        p.op = PO_NOT; p.col_a = p.col_b = -1;
-        out.push_back(p);
-        return DQ_OK;
-      }
-      case DQ_PRED_REGEX: {  // PatternMatch.scala:48-49 / RLIKE on a string column
-        if (dq_status s = check_idx(n.a)) return s;
-        const dq_pred_node& c = pool[n.a];
-        if (c.kind != DQ_PRED_COLUMN) return set_error(DQ_E_UNSUPPORTED, "regex on a non-column expression");
-        if (dq_status s = check_col(c.a)) return s;
-        const int32_t t = (*schema)[c.a].type;
-        if (t != DQ_TYPE_UTF8 && t != DQ_TYPE_LARGE_UTF8)
-          return set_error(DQ_E_UNSUPPORTED, "regex on a non-string column (%d)", c.a);
-        if (n.cmp != DQ_REGEX_RLIKE && n.cmp != DQ_REGEX_EXTRACT_NONEMPTY && n.cmp != DQ_REGEX_FULL)
-          return set_error(DQ_E_INVALID, "regex mode %d", n.cmp);
-        if (!patterns || n.i64 < 0 || n.i64 >= (int64_t)patterns->size())
-          return set_error(DQ_E_INVALID, "regex pattern index %lld out of range", (long long)n.i64);
-        auto key = std::make_pair(n.i64, n.cmp);
-        auto it = regex_at.find(key);
-        int64_t off;
-        if (it != regex_at.end()) {
-          off = it->second;
-        } else {
-          RegexDfa d;
-          if (dq_status s = regex_compile((*patterns)[n.i64].c_str(), n.cmp, d)) return s;
-          off = (int64_t)regex_blob->size();
-          regex_serialize(d, *regex_blob);
-          regex_at[key] = off;
-        }
-        PredInstr p{};
-        p.op = PO_ATOM_REGEX; p.col_a = c.a; p.col_b = -1; p.kind_a = kind_of(t);
-        p.lit_i = off;
-        p.null_res = n.cmp == DQ_REGEX_EXTRACT_NONEMPTY ? NR_FALSE : NR_NULL;
-        out.push_back(p);
-        return DQ_OK;
-      }
-      case DQ_PRED_IS_NULL:
-      case DQ_PRED_IS_NOT_NULL: {
-        if (dq_status s = check_idx(n.a)) return s;
-        const dq_pred_node& c = pool[n.a];
-        bool isnull = n.kind == DQ_PRED_IS_NULL;
-        if (c.kind == DQ_PRED_COLUMN) {
-          if (dq_status s = check_col(c.a)) return s;
-          PredInstr p{};
-          p.op = isnull ? PO_ATOM_ISNULL : PO_ATOM_NOTNULL; p.col_a = c.a; p.col_b = -1;
-          out.push_back(p);
-          return DQ_OK;
-        }
-        if (is_lit(n.a)) {
-          bool lit_null = c.kind == DQ_PRED_LIT_NULL;
-          push_const((lit_null == isnull) ? NR_TRUE : NR_FALSE);
-          return DQ_OK;
-        }
-        if (c.kind == DQ_PRED_COALESCE && is_lit(c.b) && pool[c.b].kind != DQ_PRED_LIT_NULL) {
-          push_const(isnull ? NR_FALSE : NR_TRUE);  // COALESCE(col, non-null literal) is never NULL
-          return DQ_OK;
-        }
-        return set_error(DQ_E_UNSUPPORTED, "IS NULL over an unsupported expression");
-      }
-      case DQ_PRED_LIT_BOOL: push_const(n.i64 ? NR_TRUE : NR_FALSE); return DQ_OK;
-      case DQ_PRED_LIT_NULL: push_const(NR_NULL); return DQ_OK;
-      case DQ_PRED_COLUMN: {  // a BooleanType column as a predicate: its value (NULL stays NULL), i.e. col = TRUE
-        if (dq_status s = check_col(n.a)) return s;
-        if ((*schema)[n.a].type != DQ_TYPE_BOOL)
-          return set_error(DQ_E_UNSUPPORTED, "column %d is not a boolean expression", n.a);
-        PredInstr p{};
-        p.op = PO_ATOM_CMP; p.col_a = n.a; p.col_b = -1; p.kind_a = CK_BOOL; p.kind_b = 0;
-        p.null_res = NR_NULL; p.ctype = CT_INT; p.cmp = C_EQ; p.lit_i = 1;
-        out.push_back(p);
-        return DQ_OK;
-      }
-      case DQ_PRED_CMP: {
-        if (dq_status s = check_idx(n.a)) return s;
-        if (dq_status s = check_idx(n.b)) return s;
-        int cmp = n.cmp;
-        if (cmp < DQ_CMP_LT || cmp > DQ_CMP_NE) return set_error(DQ_E_INVALID, "bad comparison op %d", cmp);
-        bool la = is_lit(n.a), lb = is_lit(n.b);
-        if (la && lb) {
-          Lit a, b;
-          if (dq_status s = lit_of(n.a, a)) return s;
-          if (dq_status s = lit_of(n.b, b)) return s;
-          push_const(lit_cmp_result(cmp, a, b));
-          return DQ_OK;
-        }
-        if (la || lb) {
-          int32_t oi = la ? n.b : n.a, li = la ? n.a : n.b;
-          if (la) cmp = flip_cmp(cmp);
-          Operand o;
-          Lit l;
-          if (dq_status s = operand_of(oi, o)) return s;
-          if (dq_status s = lit_of(li, l)) return s;
-          return emit_col_lit(o, cmp, l);
-        }
-        // column vs column
-        if (pool[n.a].kind != DQ_PRED_COLUMN || pool[n.b].kind != DQ_PRED_COLUMN)
-          return set_error(DQ_E_UNSUPPORTED, "comparison of two non-column expressions");
-        int32_t ca = pool[n.a].a, cb = pool[n.b].a;
-        if (dq_status s = check_col(ca)) return s;
-        if (dq_status s = check_col(cb)) return s;
-        int32_t ta = (*schema)[ca].type, tb = (*schema)[cb].type;
-        const bool bools = ta == DQ_TYPE_BOOL && tb == DQ_TYPE_BOOL;
-        if (!bools && (!is_numeric(ta) || !is_numeric(tb)))
-          return set_error(DQ_E_UNSUPPORTED, "comparison of non-numeric columns");
-        if (is_decimal(ta) || is_decimal(tb))
-          return set_error(DQ_E_UNSUPPORTED, "comparison of a decimal column with a column");
-        // FloatType vs Int / LongType compares in FloatType (the integer rounded to float), which a double
-        // compare does not restate for integers beyond 2^24: the fallback (ShortType / ByteType are exact)
-        auto wide_int = [](int32_t t) { return t == DQ_TYPE_I32 || t == DQ_TYPE_I64; };
-        if ((ta == DQ_TYPE_F32 && wide_int(tb)) || (tb == DQ_TYPE_F32 && wide_int(ta)))
-          return set_error(DQ_E_UNSUPPORTED, "float column compared with an int / long column");
-        PredInstr p{};
-        p.op = PO_ATOM_CMP; p.col_a = ca; p.col_b = cb; p.kind_a = kind_of(ta); p.kind_b = kind_of(tb);
-        p.null_res = NR_NULL; p.cmp = to_cmpop(cmp);
-        p.ctype = bools || (is_integral(ta) && is_integral(tb)) ? CT_INT : CT_DBL;
-        out.push_back(p);
-        return DQ_OK;
-      }
-      default:
-        return set_error(DQ_E_UNSUPPORTED, "predicate node kind %d is not a boolean expression", n.kind);
-    }
-  }
-};
-
-// canonical text of a predicate subtree (dedup of roots)
-static std::string canon(const dq_pred_node* pool, int32_t n_pred, int32_t idx, int depth = 0) {
-  if (idx < 0 || idx >= n_pred || depth > 64) return "?";
-  const dq_pred_node& n = pool[idx];
-  char buf[128];
-  std::snprintf(buf, sizeof(buf), "(%d:%d:%lld:%a", n.kind, n.cmp, (long long)n.i64, n.f64);
-  std::string s = buf;
-  if (n.kind == DQ_PRED_COLUMN) s += ":c" + std::to_string(n.a);
-  else {
-    if (n.kind == DQ_PRED_CMP || n.kind == DQ_PRED_AND || n.kind == DQ_PRED_OR || n.kind == DQ_PRED_NOT ||
-        n.kind == DQ_PRED_IS_NULL || n.kind == DQ_PRED_IS_NOT_NULL || n.kind == DQ_PRED_COALESCE ||
-        n.kind == DQ_PRED_REGEX)
-      s += canon(pool, n_pred, n.a, depth + 1);
-    if (n.kind == DQ_PRED_CMP || n.kind == DQ_PRED_AND || n.kind == DQ_PRED_OR || n.kind == DQ_PRED_COALESCE)
-      s += canon(pool, n_pred, n.b, depth + 1);
-  }
-  return s + ")";
-}
 
 }  // namespace dq
 
@@ -813,13 +270,6 @@ static dq_status reset_acc(dq_plan* p) {
   return DQ_OK;
 }
 
-template <typename T>
-static dq_status dmalloc(T** ptr, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  DQ_HIP(hipMalloc((void**)ptr, bytes));
-  return DQ_OK;
-}
-
 // Plan one pair group for the Correlation pass (dq_pair.hip): wave w's position p holds local column
 // (p + w) % 8, so every pair of two distinct columns has exactly one (wave, slot) of the fixed pattern; the
 // slot computes (position A, position B) and a pair whose first column sits at B swaps x / y on output.
@@ -893,43 +343,29 @@ static void plan_pair_wgs(const dq_plan* p, const PairGroup& g, std::vector<Pair
 
 static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred) {
   const int32_t ncols = (int32_t)p->schema.size();
-  std::map<std::string, int32_t> root_slot;          // canonical predicate text -> root slot
-  std::vector<std::vector<PredInstr>> root_code;
   std::map<std::tuple<int32_t, int32_t, int32_t>, int32_t> col_task_of;  // (col, where bitmap, f64 DataType) -> task
   std::map<std::tuple<int32_t, int32_t, int32_t>, int32_t> pair_of; // (x, y, where bitmap) -> task
   std::map<std::pair<int32_t, int32_t>, int32_t> counter_of;      // (pred slot, where slot) -> counter
   std::map<int32_t, int32_t> bitmap_of;                             // where slot -> bitmap index
   struct Needs { bool stats = false, hll = false, dtype = false; };
   std::vector<Needs> col_task_needs;
-  Lowering low{pool, n_pred, &p->schema, {}};
-  low.patterns = &p->patterns;
-  low.regex_blob = &p->regex_blob;
+  PredBuilder pb(pool, n_pred, &p->schema, &p->patterns, &p->regex_blob);
 
-  auto root = [&](int32_t node, int32_t& slot) -> dq_status {
-    if (node < 0 || node >= n_pred) return set_error(DQ_E_INVALID, "predicate root %d out of range", node);
-    std::string key = canon(pool, n_pred, node);
-    auto it = root_slot.find(key);
-    if (it != root_slot.end()) { slot = it->second; return DQ_OK; }
-    if ((int32_t)root_slot.size() >= kMaxRoots) return cap_error("more than %d distinct predicates", kMaxRoots);
-    low.out.clear();
-    if (dq_status s = low.lower(node, 0)) return s;
-    slot = (int32_t)root_slot.size();
-    root_slot[key] = slot;
-    root_code.push_back(low.out);
-    return DQ_OK;
+  // a program limit the builder ran into: roots, instructions and DFA words are capacities (dq_plan_create splits);
+  // a predicate too deep for the stack does not fit any plan (DQ_E_UNSUPPORTED: the fallback)
+  auto pred_limit = [&](dq_status s) -> dq_status {
+    switch (pb.limit) {
+      case PL_ROOTS: return cap_error("more than %d distinct predicates", kMaxRoots);
+      case PL_INSTR: return cap_error("predicate program too long (%zu instructions, at most %d)", pb.limit_value, kMaxInstr);
+      case PL_STACK:
+        return set_error(DQ_E_UNSUPPORTED, "predicate nesting needs a stack of %d (at most %d)", (int)pb.limit_value, kPredStack);
+      case PL_REGEX:
+        return cap_error("compiled patterns need %zu KB (LDS budget %d KB)", pb.limit_value * 2 / 1024, kMaxRegexWords * 2 / 1024);
+      default: return s;
+    }
   };
-  auto notnull_root = [&](int32_t col, int32_t& slot) -> dq_status {
-    std::string key = "notnull:" + std::to_string(col);
-    auto it = root_slot.find(key);
-    if (it != root_slot.end()) { slot = it->second; return DQ_OK; }
-    if ((int32_t)root_slot.size() >= kMaxRoots) return cap_error("more than %d distinct predicates", kMaxRoots);
-    PredInstr ins{};
-    ins.op = PO_ATOM_NOTNULL; ins.col_a = col; ins.col_b = -1;
-    slot = (int32_t)root_slot.size();
-    root_slot[key] = slot;
-    root_code.push_back({ins});
-    return DQ_OK;
-  };
+  auto root = [&](int32_t node, int32_t& slot) { return pred_limit(pb.root(node, slot)); };
+  auto notnull_root = [&](int32_t col, int32_t& slot) { return pred_limit(pb.notnull_root(col, slot)); };
   auto counter = [&](int32_t pred, int32_t where, int32_t& c) -> dq_status {
     auto key = std::make_pair(pred, where);
     auto it = counter_of.find(key);
@@ -1109,41 +545,17 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   }
 
   // predicate program: roots in slot order, each followed by STORE
-  p->has_pred = !root_code.empty() && (!counter_of.empty() || !bitmap_of.empty());
+  // (every root feeds a counter or a bitmap, so a plan with roots -- and only such a plan has DFAs -- assembles)
+  p->has_pred = pb.n_roots() > 0 && (!counter_of.empty() || !bitmap_of.empty());
   PredProgram& prog = p->prog;
   std::memset(&prog, 0, sizeof(prog));
   if (p->has_pred) {
-    std::vector<PredInstr> code;
-    for (size_t r = 0; r < root_code.size(); ++r) {
-      for (const PredInstr& ins : root_code[r]) code.push_back(ins);
-      PredInstr st{};
-      st.op = PO_STORE; st.slot = (int32_t)r; st.col_a = st.col_b = -1;
-      code.push_back(st);
-    }
-    if ((int32_t)code.size() > kMaxInstr) return cap_error("predicate program too long (%zu instructions, at most %d)", code.size(), kMaxInstr);
-    int depth = 0, max_depth = 0;
-    for (const PredInstr& ins : code) {
-      depth += (ins.op == PO_AND || ins.op == PO_OR || ins.op == PO_STORE) ? -1 : (ins.op == PO_NOT ? 0 : 1);
-      max_depth = std::max(max_depth, depth);
-    }
-    if (max_depth > kPredStack)
-      return set_error(DQ_E_UNSUPPORTED, "predicate nesting needs a stack of %d (at most %d)", max_depth, kPredStack);
-    prog.stack_depth = std::max(1, max_depth);
-    prog.n_roots = (int32_t)root_code.size();
-    prog.n_instr = (int32_t)code.size();
-    std::copy(code.begin(), code.end(), prog.instr);
-    for (int32_t i = 0; i < prog.n_instr; ++i)
-      if (prog.instr[i].op == PO_ATOM_CMP || prog.instr[i].op == PO_ATOM_ISNULL || prog.instr[i].op == PO_ATOM_NOTNULL ||
-          prog.instr[i].op == PO_ATOM_REGEX)
-        prog.load_instr[prog.n_loads++] = (int16_t)i;
+    if (dq_status s = pred_limit(pb.assemble(prog))) return s;
     prog.n_counters = (int32_t)counter_of.size();
     for (auto& kv : counter_of) prog.counters[kv.second] = PredCounter{kv.first.first, kv.first.second};
     prog.n_bitmaps = (int32_t)bitmap_of.size();
     for (auto& kv : bitmap_of) prog.bitmap_root[kv.second] = kv.first;
   }
-  if (p->regex_blob.size() > (size_t)kMaxRegexWords)
-    return cap_error("compiled patterns need %zu KB (LDS budget %d KB)", p->regex_blob.size() * 2 / 1024,
-                     kMaxRegexWords * 2 / 1024);
   if (p->probe) {  // capacity probe (dq_plan_create's split): every capacity check is above
     // COMPILED: the generated kernel's own limits (<= 8 value columns, 16 counters, ...) are capacities too,
     // so the greedy split never grows a part past what pred_jit_eligible takes
@@ -1409,14 +821,7 @@ static dq_status build_plan(dq_plan* p, const dq_pred_node* pool, int32_t n_pred
   if (dq_status s = dmalloc(&p->d_pred_acc, kPredAccCopies * sizeof(PredPartial))) return s;
   if (nct) DQ_HIP(hipMemcpyAsync(p->d_col_tasks, p->col_tasks.data(), nct * sizeof(ColTask), hipMemcpyHostToDevice, p->stream));
   if (npt) DQ_HIP(hipMemcpyAsync(p->d_pair_tasks, p->pair_tasks.data(), npt * sizeof(PairTask), hipMemcpyHostToDevice, p->stream));
-  if (!p->regex_blob.empty()) {
-    if (dq_status s = dmalloc(&p->d_regex, p->regex_blob.size() * sizeof(uint16_t))) return s;
-    DQ_HIP(hipMemcpyAsync(p->d_regex, p->regex_blob.data(), p->regex_blob.size() * sizeof(uint16_t),
-                           hipMemcpyHostToDevice, p->stream));
-  }
-  p->prog.regex = p->d_regex;
-  p->prog.regex_words = (int32_t)p->regex_blob.size();
-  DQ_HIP(hipMemcpyAsync(p->d_prog, &p->prog, sizeof(PredProgram), hipMemcpyHostToDevice, p->stream));
+  if (dq_status s = upload_pred_program(p->prog, p->regex_blob, &p->d_regex, p->d_prog, p->stream)) return s;
   if (dq_status s = reset_acc(p)) return s;
   DQ_HIP(hipStreamSynchronize(p->stream));
   return DQ_OK;
@@ -1585,8 +990,6 @@ static dq_status partition_specs(const dq_plan& parent, const dq_pred_node* pool
   close();
   return DQ_OK;
 }
-
-static int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // dq_plan_explain's description of one (host-only) plan
 static std::string explain_text(const dq_plan& plan) {
@@ -1766,23 +1169,19 @@ dq_status dq_plan_set_stream(dq_plan* p, void* hip_stream) {
 
 }  // extern "C"
 
-// dq_scan's contract for one column view (dqscan.h dq_column_view)
-static dq_status check_view(const dq_column_desc& cd, const dq_column_view& v, int32_t c, int64_t n_rows) {
-  const int32_t t = cd.type;
-  if (is_dict(t)) {  // reserved = the number of entries, offsets = the entry words
-    if (v.reserved < 0 || v.reserved > INT32_MAX)
-      return set_error(DQ_E_INVALID, "dq_scan: dictionary column %d has %lld entries", c, (long long)v.reserved);
-    if ((v.reserved > 0 && !v.offsets) || ((uintptr_t)v.offsets & 3) != 0)
-      return set_error(DQ_E_INVALID, "dq_scan: dictionary column %d needs a 4-byte aligned entry table", c);
-  } else if (v.reserved != 0) return set_error(DQ_E_INVALID, "dq_scan: column %d reserved field must be 0", c);
-  if (n_rows > 0 && !v.values) return set_error(DQ_E_INVALID, "dq_scan: column %d has no values buffer", c);
-  if (((uintptr_t)v.values & 15) != 0)
-    return set_error(DQ_E_INVALID, "dq_scan: column %d values buffer must be 16-byte aligned", c);
-  if (((uintptr_t)v.validity & 3) != 0)
-    return set_error(DQ_E_INVALID, "dq_scan: column %d validity bitmap must be 4-byte aligned", c);
-  if ((t == DQ_TYPE_UTF8 || t == DQ_TYPE_LARGE_UTF8) && n_rows > 0 && !v.offsets)
-    return set_error(DQ_E_INVALID, "dq_scan: UTF8 column %d has no offsets", c);
-  return DQ_OK;
+// A background compile of the predicate pass: the compiled kernel is taken once it is ready (waiting up to
+// timeout_ms for it) and runs from chunk `chunk` on; a failed compile leaves the interpreter, with its note.
+static void adopt_pred_jit(dq_plan* p, int32_t timeout_ms, int64_t chunk) {
+  if (!p->pred_jit_ref) return;
+  std::string note;
+  if (hipFunction_t fn = pred_jit_poll(p->pred_jit_ref, timeout_ms, note)) {
+    p->pred_jit = fn;
+    p->pred_jit_note = note + " (compiled in the background; used from chunk " + std::to_string(chunk) + ")";
+    p->pred_jit_ref.reset();
+  } else if (!pred_jit_pending(p->pred_jit_ref)) {
+    p->pred_jit_note = note;
+    p->pred_jit_ref.reset();
+  }
 }
 
 extern "C" {
@@ -1821,28 +1220,12 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
   }
   ScanCols sc{};
   DictSizes dsz{};
+  if (dq_status s = fill_scan_cols(p->schema, cols, n_rows, nullptr, sc)) return s;  // (every view checked)
   for (int32_t c = 0; c < ncols; ++c)
-    if (dq_status s = check_view(p->schema[c], cols[c], c, n_rows)) return s;
-  for (int32_t c = 0; c < ncols; ++c) {
-    const dq_column_view& v = cols[c];
-    if (is_dict(p->schema[c].type)) dsz.n[c] = (int32_t)v.reserved;
-    sc.values[c] = v.values;
-    sc.validity[c] = p->schema[c].nullable ? reinterpret_cast<const uint32_t*>(v.validity) : nullptr;
-    sc.offsets[c] = v.offsets;
-  }
+    if (is_dict(p->schema[c].type)) dsz.n[c] = (int32_t)cols[c].reserved;
   p->next_chunk++;
   if (n_rows == 0) return DQ_OK;
-  if (p->pred_jit_ref) {  // a background compile: take the compiled kernel from this chunk on once it is ready
-    std::string note;
-    if (hipFunction_t fn = pred_jit_poll(p->pred_jit_ref, 0, note)) {
-      p->pred_jit = fn;
-      p->pred_jit_note = note + " (compiled in the background; used from chunk " + std::to_string(chunk_index) + ")";
-      p->pred_jit_ref.reset();
-    } else if (!pred_jit_pending(p->pred_jit_ref)) {
-      p->pred_jit_note = note;  // the compile failed: the interpreter stays
-      p->pred_jit_ref.reset();
-    }
-  }
+  adopt_pred_jit(p, 0, chunk_index);  // take the compiled kernel from this chunk on once it is ready
   // the launch groups of this scan: without the compiled kernel its HLL tasks run in the column pass
   std::vector<dq_plan::Group> groups(p->groups);
   if (!p->pred_jit) groups.insert(groups.end(), p->pred_fused_groups.begin(), p->pred_fused_groups.end());
@@ -1924,12 +1307,10 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
     fr.nr[fr.n] = vr[gi].second;
     ++fr.n;
   }
-  // predicate pass: ~2048 workgroups of whole 2048-row iterations (HBM-bound; counters leave by atomics;
-  // 1024-16384 workgroups measured within 2 % on C3)
-  int32_t nr_pred = (int32_t)std::min<int64_t>(
-      DQ_PRED_WGS, std::min<int64_t>(ceil_div(n_rows, kRowsPerIter), std::max<int64_t>(1, n_rows / DQ_MIN_RANGE_ROWS)));
-  int64_t rpr_pred = ceil_div(ceil_div(n_rows, nr_pred), kRowsPerIter) * kRowsPerIter;
-  nr_pred = (int32_t)ceil_div(n_rows, rpr_pred);
+  // predicate pass: ~2048 workgroups of whole 2048-row iterations (pred_ranges, dq_plan_host.h)
+  int32_t nr_pred;
+  int64_t rpr_pred;
+  pred_ranges(n_rows, &rpr_pred, &nr_pred);
 
   // the Correlation pass: one resident round -- as many ranges as leave every workgroup of the launch resident
   // at once (the occupancy API x CUs / pair workgroups).  Each workgroup ends with a heavy epilogue (the
@@ -1999,10 +1380,8 @@ dq_status dq_scan(dq_plan* p, const dq_column_view* cols, int64_t n_rows, int64_
             }
             return pred_jit_launch(p->pred_jit, a, nr_pred, p->stream);
           }
-          const int32_t lds = kWaves * 128 * (p->prog.stack_depth + p->prog.n_roots + p->prog.n_counters) +
-                              ((p->prog.regex_words * 2 + 15) & ~15);
-          return launch_pred_scan(p->d_prog, sc, bm, n_rows, rpr_pred, nr_pred, p->d_pred_acc, lds, p->stream,
-                                  p->prog.regex_words > 0);
+          return launch_pred_scan(p->d_prog, sc, bm, n_rows, rpr_pred, nr_pred, p->d_pred_acc, pred_lds_bytes(p->prog),
+                                  p->stream, p->prog.regex_words > 0);
         }))
       return s;
   }
@@ -2442,15 +1821,7 @@ int32_t dq_plan_pred_wait(dq_plan* p, int32_t timeout_ms) {
   }
   if (p->pred_jit_ref) {
     DQ_HIP(hipSetDevice(p->device));
-    std::string note;
-    if (hipFunction_t fn = pred_jit_poll(p->pred_jit_ref, timeout_ms, note)) {
-      p->pred_jit = fn;
-      p->pred_jit_note = note + " (compiled in the background; used from chunk " + std::to_string(p->next_chunk) + ")";
-      p->pred_jit_ref.reset();
-    } else if (!pred_jit_pending(p->pred_jit_ref)) {
-      p->pred_jit_note = note;
-      p->pred_jit_ref.reset();
-    }
+    adopt_pred_jit(p, timeout_ms, p->next_chunk);
   }
   return p->pred_jit ? 1 : 0;
 }
@@ -2482,218 +1853,6 @@ int64_t dq_plan_kernel_bytes_per_row_x1000(const dq_plan* p, int32_t kernel) {
   if (kernel == 2) return p->pair_bytes_x1000;
   if (kernel >= 16 && kernel < dq_plan::kTimers) return dq_plan_variant_bytes_per_row_x1000(p, kernel - 16);
   return 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------
-// Row programs (dq_row_outcomes): a predicate program whose "counters" are its outputs -- prog.counters[k] holds
-// output k's (predicate, where) root slots -- run by dq_row_outcomes_scan (dq_kernels.hip), which stores the rows'
-// outcomes where dq_pred_scan counts them.  Lowered on the host at creation (no device); the program, its DFAs and
-// the count accumulators go to the device of the first evaluation.
-// ------------------------------------------------------------------------------------------
-struct dq_row_program {
-  std::vector<dq_column_desc> schema;
-  std::vector<std::string> patterns;
-  std::vector<uint16_t> regex_blob;
-  PredProgram prog{};
-  int32_t device = -1;  // where d_prog / d_regex / d_acc live (-1: nowhere yet)
-  PredProgram* d_prog = nullptr;
-  uint16_t* d_regex = nullptr;
-  PredPartial* d_acc = nullptr;
-};
-
-static void row_program_free_device(dq_row_program* rp) {
-  if (rp->device < 0) return;
-  (void)hipSetDevice(rp->device);
-  if (rp->d_prog) (void)hipFree(rp->d_prog);
-  if (rp->d_regex) (void)hipFree(rp->d_regex);
-  if (rp->d_acc) (void)hipFree(rp->d_acc);
-  rp->d_prog = nullptr;
-  rp->d_regex = nullptr;
-  rp->d_acc = nullptr;
-  rp->device = -1;
-}
-
-static dq_status row_program_build(dq_row_program* rp, const dq_pred_node* pool, int32_t n_pred,
-                                   const dq_row_output* outputs, int32_t n_out) {
-  std::map<std::string, int32_t> root_slot;  // canonical predicate text -> root slot
-  std::vector<PredInstr> code;
-  Lowering low{pool, n_pred, &rp->schema, {}};
-  low.patterns = &rp->patterns;
-  low.regex_blob = &rp->regex_blob;
-  auto root = [&](int32_t node, int32_t& slot) -> dq_status {
-    if (node < 0 || node >= n_pred) return set_error(DQ_E_INVALID, "dq_row_program_create: predicate root %d out of range", node);
-    const std::string key = canon(pool, n_pred, node);
-    auto it = root_slot.find(key);
-    if (it != root_slot.end()) { slot = it->second; return DQ_OK; }
-    if ((int32_t)root_slot.size() >= kMaxRoots)
-      return set_error(DQ_E_UNSUPPORTED, "dq_row_program_create: more than %d distinct roots (split the outputs)", kMaxRoots);
-    low.out.clear();
-    if (dq_status s = low.lower(node, 0)) return s;
-    slot = (int32_t)root_slot.size();
-    root_slot[key] = slot;
-    code.insert(code.end(), low.out.begin(), low.out.end());
-    PredInstr st{};
-    st.op = PO_STORE; st.slot = slot; st.col_a = st.col_b = -1;
-    code.push_back(st);
-    return DQ_OK;
-  };
-  PredProgram& prog = rp->prog;
-  std::memset(&prog, 0, sizeof(prog));
-  for (int32_t k = 0; k < n_out; ++k) {
-    int32_t ps = -1, ws = -1;
-    if (dq_status s = root(outputs[k].pred_root, ps)) return s;
-    if (outputs[k].where_root >= 0)
-      if (dq_status s = root(outputs[k].where_root, ws)) return s;
-    prog.counters[k] = PredCounter{ps, ws};
-  }
-  if ((int32_t)code.size() > kMaxInstr)
-    return set_error(DQ_E_UNSUPPORTED, "dq_row_program_create: program too long (%zu instructions, at most %d: split the outputs)",
-                     code.size(), kMaxInstr);
-  int depth = 0, max_depth = 0;
-  for (const PredInstr& ins : code) {
-    depth += (ins.op == PO_AND || ins.op == PO_OR || ins.op == PO_STORE) ? -1 : (ins.op == PO_NOT ? 0 : 1);
-    max_depth = std::max(max_depth, depth);
-  }
-  if (max_depth > kPredStack)
-    return set_error(DQ_E_UNSUPPORTED, "predicate nesting needs a stack of %d (at most %d)", max_depth, kPredStack);
-  if (rp->regex_blob.size() > (size_t)kMaxRegexWords)
-    return set_error(DQ_E_UNSUPPORTED, "dq_row_program_create: compiled patterns need %zu KB (LDS budget %d KB: split the outputs)",
-                     rp->regex_blob.size() * 2 / 1024, kMaxRegexWords * 2 / 1024);
-  prog.stack_depth = std::max(1, max_depth);
-  prog.n_roots = (int32_t)root_slot.size();
-  prog.n_instr = (int32_t)code.size();
-  std::copy(code.begin(), code.end(), prog.instr);
-  for (int32_t i = 0; i < prog.n_instr; ++i)
-    if (prog.instr[i].op == PO_ATOM_CMP || prog.instr[i].op == PO_ATOM_ISNULL || prog.instr[i].op == PO_ATOM_NOTNULL ||
-        prog.instr[i].op == PO_ATOM_REGEX)
-      prog.load_instr[prog.n_loads++] = (int16_t)i;
-  prog.n_counters = n_out;
-  prog.regex_words = (int32_t)rp->regex_blob.size();
-  return DQ_OK;
-}
-
-extern "C" {
-
-int32_t dq_row_max_outputs(void) { return kMaxRoots; }
-
-dq_status dq_row_program_create(const dq_column_desc* schema, int32_t n_cols, const dq_pred_node* pred_pool,
-                                int32_t n_pred, const char* const* patterns, int32_t n_patterns,
-                                const dq_row_output* outputs, int32_t n_out, dq_row_program** out) {
-  if (!out) return set_error(DQ_E_INVALID, "dq_row_program_create: out is NULL");
-  *out = nullptr;
-  if (n_cols < 0 || (n_cols > 0 && !schema)) return set_error(DQ_E_INVALID, "dq_row_program_create: bad schema");
-  if (n_cols > kMaxCols)
-    return set_error(DQ_E_UNSUPPORTED, "dq_row_program_create: more than %d columns (pass the columns the outputs read)", kMaxCols);
-  if (n_pred < 0 || (n_pred > 0 && !pred_pool)) return set_error(DQ_E_INVALID, "dq_row_program_create: bad predicate pool");
-  if (n_patterns < 0 || (n_patterns > 0 && !patterns)) return set_error(DQ_E_INVALID, "dq_row_program_create: bad patterns");
-  for (int32_t k = 0; k < n_patterns; ++k)
-    if (!patterns[k]) return set_error(DQ_E_INVALID, "dq_row_program_create: pattern %d is NULL", k);
-  if (n_out < 1 || !outputs) return set_error(DQ_E_INVALID, "dq_row_program_create: no outputs");
-  if (n_out > kMaxCounters)
-    return set_error(DQ_E_UNSUPPORTED, "dq_row_program_create: more than %d outputs (split them)", kMaxCounters);
-  for (int32_t c = 0; c < n_cols; ++c)
-    if (!plan_type_valid(schema[c].type))
-      return set_error(DQ_E_TYPE, "dq_row_program_create: column %d has unknown type %d", c, schema[c].type);
-  std::unique_ptr<dq_row_program> rp(new dq_row_program());
-  rp->schema.assign(schema, schema + n_cols);
-  for (int32_t k = 0; k < n_patterns; ++k) rp->patterns.emplace_back(patterns[k]);
-  if (dq_status s = row_program_build(rp.get(), pred_pool, n_pred, outputs, n_out)) return s;
-  *out = rp.release();
-  return DQ_OK;
-}
-
-dq_status dq_row_program_info(const dq_row_program* rp, int32_t* n_outputs, int32_t* n_roots, int32_t* n_instr) {
-  if (!rp) return set_error(DQ_E_INVALID, "dq_row_program_info: program is NULL");
-  if (n_outputs) *n_outputs = rp->prog.n_counters;
-  if (n_roots) *n_roots = rp->prog.n_roots;
-  if (n_instr) *n_instr = rp->prog.n_instr;
-  return DQ_OK;
-}
-
-void dq_row_program_destroy(dq_row_program* rp) {
-  if (!rp) return;
-  row_program_free_device(rp);
-  delete rp;
-}
-
-dq_status dq_row_outcomes(dq_row_program* rp, const dq_column_view* cols, int64_t n_rows, uint64_t* const* pass,
-                          uint64_t* const* applies, int32_t device, void* hip_stream, int64_t* num_pass,
-                          int64_t* num_applies) {
-  if (!rp) return set_error(DQ_E_INVALID, "dq_row_outcomes: program is NULL");
-  if (n_rows < 0) return set_error(DQ_E_INVALID, "dq_row_outcomes: n_rows < 0");
-  if (n_rows >= (int64_t(1) << 31))
-    return set_error(DQ_E_INVALID, "dq_row_outcomes: a chunk holds at most 2^31 - 1 rows (split larger inputs into chunks)");
-  const int32_t ncols = (int32_t)rp->schema.size(), n_out = rp->prog.n_counters;
-  if (n_rows == 0) {
-    for (int32_t k = 0; k < n_out; ++k) {
-      if (num_pass) num_pass[k] = 0;
-      if (num_applies) num_applies[k] = 0;
-    }
-    return DQ_OK;
-  }
-  if (ncols > 0 && !cols) return set_error(DQ_E_INVALID, "dq_row_outcomes: cols is NULL");
-  if (!pass) return set_error(DQ_E_INVALID, "dq_row_outcomes: pass is NULL");
-  for (int32_t k = 0; k < n_out; ++k) {
-    if (!pass[k] || ((uintptr_t)pass[k] & 7) != 0)
-      return set_error(DQ_E_INVALID, "dq_row_outcomes: pass[%d] must be an 8-byte aligned device buffer", k);
-    if (applies && ((uintptr_t)applies[k] & 7) != 0)
-      return set_error(DQ_E_INVALID, "dq_row_outcomes: applies[%d] must be 8-byte aligned", k);
-  }
-  // the columns the program reads (the others' views may be empty)
-  std::vector<char> used(ncols, 0);
-  for (int32_t i = 0; i < rp->prog.n_instr; ++i) {
-    if (rp->prog.instr[i].col_a >= 0) used[rp->prog.instr[i].col_a] = 1;
-    if (rp->prog.instr[i].col_b >= 0) used[rp->prog.instr[i].col_b] = 1;
-  }
-  ScanCols sc{};
-  for (int32_t c = 0; c < ncols; ++c) {
-    if (!used[c]) continue;
-    if (dq_status s = check_view(rp->schema[c], cols[c], c, n_rows)) return s;
-    sc.values[c] = cols[c].values;
-    sc.validity[c] = rp->schema[c].nullable ? reinterpret_cast<const uint32_t*>(cols[c].validity) : nullptr;
-    sc.offsets[c] = cols[c].offsets;
-  }
-  int ndev = 0;
-  DQ_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return set_error(DQ_E_INVALID, "dq_row_outcomes: device %d of %d", device, ndev);
-  const hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  if (rp->device != device) {
-    row_program_free_device(rp);
-    DQ_HIP(hipSetDevice(device));
-    rp->device = device;
-    if (dq_status s = dmalloc(&rp->d_prog, sizeof(PredProgram))) return s;
-    if (dq_status s = dmalloc(&rp->d_acc, kPredAccCopies * sizeof(PredPartial))) return s;
-    if (!rp->regex_blob.empty()) {
-      if (dq_status s = dmalloc(&rp->d_regex, rp->regex_blob.size() * sizeof(uint16_t))) return s;
-      DQ_HIP(hipMemcpy(rp->d_regex, rp->regex_blob.data(), rp->regex_blob.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-    rp->prog.regex = rp->d_regex;
-    DQ_HIP(hipMemcpy(rp->d_prog, &rp->prog, sizeof(PredProgram), hipMemcpyHostToDevice));
-  }
-  DQ_HIP(hipSetDevice(device));
-  // dq_scan's predicate-pass ranges: whole 2048-row iterations, at most DQ_PRED_WGS workgroups
-  int32_t nr = (int32_t)std::min<int64_t>(
-      DQ_PRED_WGS, std::min<int64_t>(ceil_div(n_rows, kRowsPerIter), std::max<int64_t>(1, n_rows / DQ_MIN_RANGE_ROWS)));
-  const int64_t rpr = ceil_div(ceil_div(n_rows, nr), kRowsPerIter) * kRowsPerIter;
-  nr = (int32_t)ceil_div(n_rows, rpr);
-  const int32_t lds = kWaves * 128 * (rp->prog.stack_depth + rp->prog.n_roots + rp->prog.n_counters) +
-                      ((rp->prog.regex_words * 2 + 15) & ~15);
-  DQ_HIP(hipMemsetAsync(rp->d_acc, 0, kPredAccCopies * sizeof(PredPartial), st));
-  DQ_HIP(launch_row_outcomes(rp->d_prog, sc, reinterpret_cast<uint32_t* const*>(pass),
-                             reinterpret_cast<uint32_t* const*>(applies), n_out, n_rows, rpr, nr, rp->d_acc, lds, st,
-                             rp->prog.regex_words > 0));
-  std::vector<PredPartial> acc(kPredAccCopies);
-  DQ_HIP(hipMemcpyAsync(acc.data(), rp->d_acc, kPredAccCopies * sizeof(PredPartial), hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  for (int32_t k = 0; k < n_out; ++k) {
-    int64_t t = 0, a = 0;
-    for (int c = 0; c < kPredAccCopies; ++c) { t += acc[c].t[k]; a += acc[c].nn[k]; }
-    if (num_pass) num_pass[k] = t;
-    if (num_applies) num_applies[k] = a;
-  }
-  return DQ_OK;
 }
 
 }  // extern "C"

@@ -96,7 +96,7 @@ __device__ __forceinline__ uint64_t rows_mask(int32_t left) {
   return left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
 }
 // validity words of a block (lanes 0..15: rows base + 32 l .. + 31).  A column without a bitmap gets the plan's
-// all-ones bitmap (dq_plan.cpp), so the load is unconditional: no branch around it for the waitcnt pass to
+// all-ones bitmap (dq_scan, dq_plan.cpp), so the load is unconditional: no branch around it for the waitcnt pass to
 // merge.  The 64-bit mask of row group j is then two readlanes: scalar loads of every group's words, hoisted
 // by the compiler, overflowed the scalar file.
 __device__ __forceinline__ uint32_t valid_words(const uint32_t* bm, int64_t base, int64_t n_rows, int lane) {
@@ -277,7 +277,7 @@ std::string pred_jit_source(const PredProgram& prog, const int32_t* col_kind, st
            std::to_string(sz) + "), (short)0, (int)((row1 - row0) * " + std::to_string(sz) + "), 0x00020000);\n";
   }
   // per-wave counters in 32 bits: a wave counts at most a quarter of its range's rows, and the planner's
-  // ranges (>= 64 per chunk, dq_plan.cpp size_ranges) keep that far below 2^32 for any chunk HBM can hold
+  // ranges (dq_plan_host.h pred_ranges: whole 2048-row iterations of a chunk of < 2^31 rows) keep that below 2^32
   for (int c = 0; c < prog.n_counters; ++c) s += "  uint32_t ct" + std::to_string(c) + " = 0, cn" + std::to_string(c) + " = 0;\n";
   for (int h = 0; h < nh; ++h) s += "  uint32_t hc" + std::to_string(h) + " = 0;\n";
   // values and validity words one block ahead, per row group: v[i][j] of the next block is loaded as soon as

@@ -1,4 +1,4 @@
-"""Predicate type coercion at precision boundaries (Lowering::emit_col_lit in deequ_amd/csrc/dq_plan.cpp).
+"""Predicate type coercion at precision boundaries (Lowering::emit_col_lit in deequ_amd/csrc/dq_pred_lower.cpp).
 
 Spark 2.2 picks the type a comparison runs in from both sides (findTightestCommonType, DecimalPrecision; restated
 in oracle.dq_oracle._widen): integral vs integer / decimal exactly, anything vs double in double, a FloatType

@@ -54,8 +54,8 @@ def nullable_f64(rng, n):
 
 # ---- tail and layout ------------------------------------------------------------------------------------------------
 
-# dq_row_outcomes launches dq_scan's predicate-pass ranges: max(1, n / DQ_MIN_RANGE_ROWS) of them (dq_plan.cpp,
-# DQ_MIN_RANGE_ROWS = 16384), so 2 * 16384 + 17 rows run as two workgroup ranges
+# dq_row_outcomes launches dq_scan's predicate-pass ranges: max(1, n / DQ_MIN_RANGE_ROWS) of them (pred_ranges in
+# dq_plan_host.h, DQ_MIN_RANGE_ROWS = 16384), so 2 * 16384 + 17 rows run as two workgroup ranges
 TWO_RANGES = 2 * 16384 + 17
 TAIL_SIZES = [1, 31, 32, 33, 63, 64, 65, 511, 512, 513, 2047, 2048, 2049, 3 * 2048 + 17, TWO_RANGES]
 
