@@ -42,6 +42,8 @@ constexpr int kSchemaBlock = 256;
 constexpr int kGroupsPerWave = 4;                                  // 64-row groups per wave
 constexpr int kRowsPerBlock = kSchemaBlock * kGroupsPerWave;       // 1024
 constexpr int kDfaLdsWords = 24 * 1024;                            // DFAs up to 48 KiB are staged in LDS
+// (tests/regex_cases.py SCHEMA_PATTERNS are sized around this constant -- one DFA under it, two over -- and
+// tests/test_regex_cases_host.py restates it: change them together, or the global-memory walk loses its test)
 
 // the bytes of one string through the aligned dwords that hold them (dq_cast.hip's reader, 64-bit positions)
 struct SchemaDevBytes {

@@ -14,8 +14,9 @@ def _import_dictionary(arr):
     s, a = ingest.ArrowSchemaC(), ingest.ArrowArrayC()
     arr._export_to_c(ctypes.addressof(a), ctypes.addressof(s))
     idx, dic = ingest.HostColumn(), ingest.HostColumn()
-    st = L.lib.dq_arrow_import_dictionary(ctypes.addressof(s), ctypes.addressof(a), ctypes.addressof(idx),
-                                          ctypes.addressof(dic))
+    # byref: right both for _lib's void* prototype and for the typed one ingest binds once a table was ingested
+    # (after tests/test_dict_gpu.py in the same process a plain address is refused by ctypes)
+    st = L.lib.dq_arrow_import_dictionary(ctypes.byref(s), ctypes.byref(a), ctypes.byref(idx), ctypes.byref(dic))
     return st, idx, dic, (s, a)
 
 

@@ -5,7 +5,8 @@ The compiler turns a java.util.regex pattern into the byte-level search DFA the 
 checks the compiler -- parser, UTF-8 range splitting, subset construction, `^` / `$` handling --
 against the oracle's restatement of Spark's regexp_extract (Python's backtracking `re` with Java's
 defaults, pinned by the reference's PatternMatch known answers in tests/golden/reference_kats.json).
-The GPU walk itself is checked in tests/test_gpu_parity.py::test_pattern_match_vs_oracle.
+The GPU walk itself is checked in tests/test_gpu_parity.py::test_pattern_match_vs_oracle (counts over random
+strings) and row by row at its window and LDS edges in tests/test_regex_walk_gpu.py.
 
 Known, documented gap: a trailing `$` accepts "\\n" as the final terminator even when
 the match ends with "\\r" (Java refuses to match between \\r and \\n); inputs here contain no "\\r".
