@@ -22,7 +22,8 @@ from .grouping import (CountDistinct, Distinctness, Entropy, FrequenciesAndNumRo
                        MutualInformation, Uniqueness, UniqueValueRatio)
 from .metrics import (DoubleMetric, Distribution, DistributionValue, Entity, HistogramMetric,  # noqa: F401
                       KeyedDoubleMetric)
-from .profiles import (ColumnProfiler, ColumnProfiles, NumericColumnProfile, StandardColumnProfile,  # noqa: F401
+from .profiles import (ColumnProfiler, ColumnProfilerRunBuilder, ColumnProfilerRunner, ColumnProfiles,  # noqa: F401
+                       NumericColumnProfile, StandardColumnProfile,
                        compute_histograms)
 from .quantiles import ApproxQuantile, ApproxQuantiles  # noqa: F401
 from .runner import AnalysisRunner, AnalyzerContext, ReusingNotPossibleResultsMissingException  # noqa: F401

@@ -446,7 +446,7 @@ EXPORTED = [
     "dq_pred_pool_create", "dq_pred_pool_add", "dq_pred_pool_add_regex", "dq_pred_pool_size", "dq_pred_pool_nodes",
     "dq_pred_pool_num_patterns", "dq_pred_pool_patterns", "dq_pred_pool_destroy",
     "dq_arrow_import", "dq_uploader_create", "dq_upload", "dq_upload_fence", "dq_upload_release", "dq_upload_sync",
-    "dq_uploader_destroy",
+    "dq_uploader_destroy", "dq_upload_payload", "dq_upload_stage", "dq_upload_to",
     "dq_plan_set_stream", "dq_freq_build", "dq_freq_merge", "dq_freq_summarize", "dq_freq_num_groups",
     "dq_freq_export", "dq_freq_destroy", "dq_freq_materialize", "dq_freq_self_contained", "dq_freq_to_bytes",
     "dq_freq_from_bytes", "dq_freq_take_values", "dq_freq_mutual_information", "dq_mutual_information", "dq_approx_quantiles", "dq_quantile_digest", "dq_freq_top", "dq_scan", "dq_finish",

@@ -21,7 +21,7 @@ from .analyzers import DataType, DataTypeInstances
 from .grouping import (Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
 from .quantiles import ApproxQuantile
-from .runner import AnalysisRunner, AnalyzerContext
+from .runner import AnalysisRunner, AnalyzerContext, arrow_data
 
 
 class CheckLevel(IntEnum):  # Check.scala:30-32
@@ -412,6 +412,7 @@ class VerificationSuite:  # VerificationSuite.scala:42-282
                           aggregateWith=None, saveStatesWith=None, metricsRepository=None,
                           reuseExistingResultsForKey=None, failIfResultsForReusingMissing: bool = False,
                           saveOrAppendResultsWithKey=None) -> VerificationResult:
+        data = arrow_data(data)
         analyzers = list(requiredAnalyzers) + [a for c in checks for a in c.requiredAnalyzers()]
         # the analysis run reuses but does not save (VerificationSuite.scala:121-130): the checks, the anomaly checks
         # among them, are evaluated against the repository as it was, and the metrics are stored after that (:132-139)
@@ -449,7 +450,7 @@ def getAnomalyCheck(metricsRepository, anomalyDetectionStrategy, analyzer,
 
 class VerificationRunBuilder:  # VerificationRunBuilder.scala:28-149
     def __init__(self, data):
-        self.data = data
+        self.data = arrow_data(data)
         self.checks: List[Check] = []
         self.required: List[Analyzer] = []
         self._aggregateWith = None

@@ -25,14 +25,13 @@
 
 #include "../../include/dqscan.h"
 #include "dq_internal.h"
+#include "dq_upload_host.h"
 
 using dq::set_error;
 
 namespace {
 
-constexpr int64_t kAlign = 256;  // every buffer of a slot starts 256-byte aligned (values need 16)
-
-int64_t align_up(int64_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+using namespace dq::up;  // the copy pieces and their thread pool (dq_upload_host.h, shared with dq_upload_stage)
 
 int32_t type_of_format(const char* f) {
   if (!f) return 0;
@@ -64,141 +63,6 @@ int32_t type_of_format(const char* f) {
     return DQ_DECIMAL128(p, sc);
   }
   return 0;
-}
-
-// bytes per value of a fixed-width type (BOOL: bit-packed, 0)
-int64_t value_width(int32_t type) {
-  switch (type) {
-    case DQ_TYPE_F64: case DQ_TYPE_I64: case DQ_TYPE_TIMESTAMP: return 8;
-    case DQ_TYPE_I32: case DQ_TYPE_F32: case DQ_TYPE_DATE32: return 4;
-    case DQ_TYPE_I16: return 2;
-    case DQ_TYPE_I8: return 1;
-    default: return dq::is_decimal(type) ? 16 : 0;
-  }
-}
-
-// parallel copy of a list of pieces over up to `threads` CPU threads.  A piece is a memcpy, or -- for an
-// Arrow slice -- a rebase of its string offsets (minus the slice's first offset) or a shift of its
-// validity bitmap (the slice's row 0 at bit `shift` of the first source byte).
-struct Piece {
-  char* dst;
-  const char* src;
-  int64_t bytes;           // destination bytes
-  int kind = 0;            // 0 memcpy, 1 int32 offsets - base, 2 int64 offsets - base, 3 bitmap >> shift
-  int64_t base = 0;        // kinds 1, 2
-  int shift = 0;           // kind 3 (1..7)
-  int64_t src_bytes = 0;   // kind 3: readable source bytes
-  // kind 4: dictionary indices widened to int32 and range-checked (dq_dict_check_indices' loop)
-  int idx_type = 0;                  // DQ_TYPE_I8 / I16 / I32, negative: unsigned
-  int64_t n_entries = 0;
-  const uint8_t* valid = nullptr;    // the rows' bitmap (row 0 at bit valid_bit) or NULL
-  int valid_bit = 0;
-  std::atomic<int64_t>* bad = nullptr;  // the lowest offending row, or INT64_MAX
-};
-
-// Rows [r0, r1) of a dictionary index array of `type` widened to int32 (out may be NULL) and checked against
-// [0, n_entries) where the row's validity bit (bit r + bit of `validity`, NULL: every row) is set; a NULL row's
-// index is written 0.  Returns the first offending row (its index in *bad_value), or -1.
-int64_t widen_check(int type, const void* src, int64_t r0, int64_t r1, const uint8_t* validity, int bit,
-                    int64_t n_entries, int32_t* out, int64_t* bad_value) {
-  auto run = [&](auto tag) -> int64_t {
-    using T = decltype(tag);
-    const char* p = static_cast<const char*>(src);
-    for (int64_t r = r0; r < r1; ++r) {
-      T t;
-      std::memcpy(&t, p + r * (int64_t)sizeof(T), sizeof(T));
-      const int64_t v = (int64_t)t, b = r + bit;
-      const bool valid = !validity || ((validity[b >> 3] >> (b & 7)) & 1);
-      if (valid && (v < 0 || v >= n_entries)) {
-        if (bad_value) *bad_value = v;
-        return r;
-      }
-      if (out) out[r] = valid ? (int32_t)v : 0;
-    }
-    return -1;
-  };
-  switch (type) {
-    case DQ_TYPE_I8: return run(int8_t{});
-    case DQ_TYPE_I16: return run(int16_t{});
-    case DQ_TYPE_I32: return run(int32_t{});
-    case -DQ_TYPE_I8: return run(uint8_t{});
-    default: return run(uint16_t{});  // -DQ_TYPE_I16 (index_type_ok)
-  }
-}
-bool index_type_ok(int t) {
-  return t == DQ_TYPE_I8 || t == DQ_TYPE_I16 || t == DQ_TYPE_I32 || t == -DQ_TYPE_I8 || t == -DQ_TYPE_I16;
-}
-
-void copy_part(const Piece& p, int64_t a, int64_t b) {  // destination bytes [a, b) of piece p
-  switch (p.kind) {
-    case 0: std::memcpy(p.dst + a, p.src + a, (size_t)(b - a)); break;
-    case 1: {
-      const int32_t base = (int32_t)p.base;
-      for (int64_t i = a / 4; i < b / 4; ++i) {
-        int32_t v;
-        std::memcpy(&v, p.src + 4 * i, 4);
-        v -= base;
-        std::memcpy(p.dst + 4 * i, &v, 4);
-      }
-      break;
-    }
-    case 2:
-      for (int64_t i = a / 8; i < b / 8; ++i) {
-        int64_t v;
-        std::memcpy(&v, p.src + 8 * i, 8);
-        v -= p.base;
-        std::memcpy(p.dst + 8 * i, &v, 8);
-      }
-      break;
-    case 4: {
-      int64_t v = 0;
-      const int64_t r = widen_check(p.idx_type, p.src, a / 4, b / 4, p.valid, p.valid_bit, p.n_entries,
-                                    reinterpret_cast<int32_t*>(p.dst), &v);
-      if (r >= 0) {
-        int64_t cur = p.bad->load();
-        while (r < cur && !p.bad->compare_exchange_weak(cur, r)) {}
-      }
-      break;
-    }
-    default: {
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(p.src);
-      for (int64_t i = a; i < b; ++i) {
-        const uint32_t lo = src[i], hi = i + 1 < p.src_bytes ? src[i + 1] : 0u;
-        p.dst[i] = (char)(uint8_t)((lo >> p.shift) | (hi << (8 - p.shift)));
-      }
-    }
-  }
-}
-
-void parallel_copy(const std::vector<Piece>& pieces, int threads) {
-  int64_t total = 0;
-  for (const Piece& p : pieces) total += p.bytes;
-  constexpr int64_t kGrain = 8 << 20;
-  const int n = (int)std::max<int64_t>(1, std::min<int64_t>(threads, total / kGrain));
-  if (n <= 1) {
-    for (const Piece& p : pieces)
-      if (p.bytes) copy_part(p, 0, p.bytes);
-    return;
-  }
-  // split the concatenated byte range [0, total) into n contiguous shares; inside a piece the share
-  // boundaries are rounded down to 8 bytes (whole offsets), the same way on both sides of a boundary
-  auto work = [&](int t) {
-    const int64_t lo = total * t / n, hi = total * (t + 1) / n;
-    int64_t at = 0;
-    for (const Piece& p : pieces) {
-      if (at + p.bytes > lo && at < hi) {
-        const int64_t a = lo <= at ? 0 : ((lo - at) & ~int64_t(7));
-        const int64_t b = hi >= at + p.bytes ? p.bytes : ((hi - at) & ~int64_t(7));
-        if (a < b) copy_part(p, a, b);
-      }
-      at += p.bytes;
-      if (at >= hi) break;
-    }
-  };
-  std::vector<std::thread> pool;
-  for (int t = 1; t < n; ++t) pool.emplace_back(work, t);
-  work(0);
-  for (std::thread& th : pool) th.join();
 }
 
 }  // namespace
@@ -459,6 +323,37 @@ dq_status dq_upload(dq_uploader* u, const dq_host_column* cols, int32_t n_cols, 
     dev_views[c].reserved = 0;
   }
   u->used[(size_t)s] = true;
+  u->bytes += at;
+  ++u->next;
+  return DQ_OK;
+}
+
+dq_status dq_upload_to(dq_uploader* u, const dq_host_column* cols, int32_t n_cols, const dq_upload_dest* dests) {
+  if (!u || (n_cols > 0 && (!cols || !dests)) || n_cols < 0) return set_error(DQ_E_INVALID, "dq_upload_to: bad argument");
+  const size_t s = (size_t)(u->next % (int64_t)u->pinned.size());
+  hipError_t e = hipSetDevice(u->device);
+  if (e != hipSuccess) return set_error(DQ_E_HIP, "hipSetDevice failed: %s", hipGetErrorString(e));
+  // the slot's previous DMA must have drained the pinned buffer before the CPU overwrites it
+  if (u->used[s] && (e = hipEventSynchronize(u->copied[s])) != hipSuccess)
+    return set_error(DQ_E_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
+  std::vector<int64_t> pos(3 * (size_t)std::max(1, n_cols), -1);
+  int64_t at = 0;
+  if (dq_status st = stage(cols, n_cols, dests, u->pinned[s], u->slot_bytes, u->threads, pos.data(), &at))
+    return st;
+  // one DMA per destination buffer, its whole image (rows and padding); the device slot is not used
+  for (int32_t c = 0; c < n_cols; ++c) {
+    void* dst[3] = {dests[c].values, dests[c].validity, dests[c].offsets};
+    const int64_t len[3] = {dests[c].value_bytes, dests[c].validity_bytes, dests[c].offset_bytes};
+    for (int k = 0; k < 3; ++k) {
+      const int64_t p = pos[3 * (size_t)c + k];
+      if (p < 0) continue;
+      if ((e = hipMemcpyAsync(dst[k], u->pinned[s] + p, (size_t)len[k], hipMemcpyHostToDevice, u->copy)) != hipSuccess)
+        return set_error(DQ_E_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e));
+    }
+  }
+  if ((e = hipEventRecord(u->copied[s], u->copy)) != hipSuccess)
+    return set_error(DQ_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(e));
+  u->used[s] = true;
   u->bytes += at;
   ++u->next;
   return DQ_OK;

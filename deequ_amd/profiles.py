@@ -20,7 +20,7 @@ from .analyzers import (ApproxCountDistinct, Completeness, DataType, DataTypeIns
 from .casts import cast_numeric_string_columns, second_pass_analyzers
 from .metrics import Distribution, DistributionValue, UnsupportedOnGpuPathException
 from .quantiles import ApproxQuantiles
-from .runner import AnalysisRunner, AnalyzerContext, _chunks
+from .runner import AnalysisRunner, AnalyzerContext, _chunks, arrow_data
 from .table import Table, decimal_ps
 
 DEFAULT_CARDINALITY_THRESHOLD = 120
@@ -339,6 +339,7 @@ class ColumnProfiler:  # ColumnProfiler.scala:66-188
         if (metricsRepository is not None or reuseExistingResultsUsingKey is not None or failIfResultsForReusingMissing
                 or saveInMetricsRepositoryUsingKey is not None):
             raise NotImplementedError("ColumnProfiler.profile: the metrics repository is not part of the GPU path")
+        data = arrow_data(data)
         if not isinstance(data, Table):
             data = list(data)  # (an iterator of chunks is read once)
             if not data:
@@ -371,3 +372,33 @@ class ColumnProfiler:  # ColumnProfiler.scala:66-188
         targets = find_target_columns_for_histograms(schema, generic, lowCardinalityHistogramThreshold)
         histograms = compute_histograms(data, targets) if targets else {}
         return create_profiles(relevant, generic, numeric, histograms)
+
+
+class ColumnProfilerRunner:  # profiles/ColumnProfilerRunner.scala:42-48
+    def onData(self, data) -> "ColumnProfilerRunBuilder":
+        return ColumnProfilerRunBuilder(data)
+
+
+class ColumnProfilerRunBuilder:  # profiles/ColumnProfilerRunBuilder.scala:27-105 (the options of the GPU path)
+    def __init__(self, data):
+        self.data = arrow_data(data)
+        self._restrictToColumns: Optional[Sequence[str]] = None
+        self._printStatusUpdates = False
+        self._threshold = DEFAULT_CARDINALITY_THRESHOLD
+
+    def restrictToColumns(self, columns: Sequence[str]) -> "ColumnProfilerRunBuilder":
+        self._restrictToColumns = list(columns)
+        return self
+
+    def printStatusUpdates(self, on: bool) -> "ColumnProfilerRunBuilder":
+        self._printStatusUpdates = on
+        return self
+
+    def withLowCardinalityHistogramThreshold(self, threshold: int) -> "ColumnProfilerRunBuilder":
+        self._threshold = threshold
+        return self
+
+    def run(self) -> ColumnProfiles:
+        return ColumnProfiler.profile(self.data, restrictToColumns=self._restrictToColumns,
+                                      printStatusUpdates=self._printStatusUpdates,
+                                      lowCardinalityHistogramThreshold=self._threshold)

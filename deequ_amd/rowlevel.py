@@ -461,7 +461,10 @@ def row_level_results(checks, data, filteredRow: str = "TRUE") -> RowLevelResult
     """Per-row outcomes of the checks' constraints over `data` (a Table or a list of chunk Tables)."""
     if filteredRow not in FILTERED_ROW:
         raise ValueError(f"filteredRow must be one of {FILTERED_ROW}")
+    from .runner import arrow_data
+
     checks = list(checks)
+    data = arrow_data(data)
     chunks = [data] if isinstance(data, Table) else list(data)
     if not chunks:
         raise ValueError("row_level_results: no chunks")

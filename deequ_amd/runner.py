@@ -36,6 +36,36 @@ def _chunks(data) -> List[Table]:
     return [data] if isinstance(data, Table) else list(data)
 
 
+def arrow_data(data):
+    """`data` as the runners take it.  Arrow data -- a pyarrow RecordBatch, Table, RecordBatchReader or a sequence of
+    RecordBatches -- is uploaded once, onto the current torch device (ingest.tables_from_arrow): a RecordBatch becomes
+    a Table, the other shapes a chunk list with one Table per record batch.  Anything else comes back as it is.  Every
+    public entry that takes data calls this first; a caller that runs several things over the same Arrow data converts
+    it once with ingest.tables_from_arrow and passes the Tables."""
+    from .ingest import is_arrow, tables_from_arrow
+
+    if isinstance(data, Table) or not is_arrow(data):
+        return data
+    import torch
+
+    tables = tables_from_arrow(data, torch.device("cuda", torch.cuda.current_device()))
+    return tables[0] if type(data).__name__ == "RecordBatch" else tables
+
+
+def arrow_data_schema(schema):
+    """runOnAggregatedStates' schema argument: a schema as it is; of data -- Tables or Arrow -- its schema, without
+    uploading anything."""
+    from .ingest import arrow_schema, is_arrow
+
+    if isinstance(schema, Table):
+        return schema.schema
+    if isinstance(schema, (list, tuple)) and schema and isinstance(schema[0], Table):
+        return schema[0].schema
+    if is_arrow(schema):
+        return arrow_schema(schema[0] if isinstance(schema, (list, tuple)) else schema)
+    return schema
+
+
 def dictionary_columns_to_decode(schema, analyzers: Sequence[Analyzer]) -> set:
     """The dict_utf8 columns of `schema` that a run of `analyzers` reads as string bytes.  A column stays encoded (the
     plan's dictionary row pass reads indices only) while the run refers to it only as the column of Completeness /
@@ -328,6 +358,7 @@ class AnalysisRunner:
                       failIfResultsForReusingMissing: bool = False, saveOrAppendResultsWithKey=None) -> AnalyzerContext:
         if not analyzers:
             return AnalyzerContext.empty()
+        data = arrow_data(data)
         all_analyzers = list(dict.fromkeys(analyzers))  # case-class equality dedup, order kept
         # AnalysisRunner.scala:116-135: a metric stored under the reuse key is not computed again; its analyzer
         # leaves the run here, before the preconditions and before any plan is built
@@ -469,6 +500,7 @@ class AnalysisRunner:
 
         if not analyzers or not stateLoaders:
             return AnalyzerContext.empty()
+        schema = arrow_data_schema(schema)
         agg = InMemoryStateProvider()
         metrics = {}
         for a in dict.fromkeys(analyzers):
@@ -499,7 +531,7 @@ class AnalysisRunner:
 
 class AnalysisRunBuilder:
     def __init__(self, data):
-        self.data = data
+        self.data = arrow_data(data)  # (Arrow data: uploaded here, once, however often the builder runs)
         self.analyzers: List[Analyzer] = []
         self._aggregateWith = None
         self._saveStatesWith = None

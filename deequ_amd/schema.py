@@ -295,7 +295,9 @@ class RowLevelSchemaValidator:
         chunk (the result tables are then lists, one Table per chunk)."""
         from .table import plain_utf8
 
-        data = plain_utf8(data)  # (dictionary-encoded string columns: read as the plain columns they stand for)
+        from .runner import arrow_data
+
+        data = plain_utf8(arrow_data(data))  # (dictionary-encoded string columns: read as the plain columns they stand for)
         single = isinstance(data, Table)
         chunks = [data] if single else list(data)
         if not chunks:

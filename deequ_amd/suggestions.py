@@ -26,7 +26,7 @@ from .checks import (Check, CheckLevel, ConstrainableDataTypes, VerificationResu
                      data_type_constraint)
 from .grouping import Uniqueness, _java_double_to_string
 from .profiles import NULL_FIELD_REPLACEMENT, ColumnProfile, ColumnProfiler, ColumnProfiles, NumericColumnProfile
-from .runner import _chunks
+from .runner import _chunks, arrow_data
 from .split import check_ratio, random_split
 from .table import Table
 
@@ -339,6 +339,7 @@ class ConstraintSuggestionRunner:  # ConstraintSuggestionRunner.scala:56-315
             overwriteResults=False) -> ConstraintSuggestionResult:  # :62-125
         if testsetRatio is not None:
             check_ratio(testsetRatio)
+        data = arrow_data(data)
         if not isinstance(data, Table):
             data = list(data)
         training, test, seed = data, None, None
@@ -384,7 +385,7 @@ class ConstraintSuggestionRunner:  # ConstraintSuggestionRunner.scala:56-315
 
 class ConstraintSuggestionRunBuilder:  # ConstraintSuggestionRunBuilder.scala:27-293
     def __init__(self, data):
-        self.data = data
+        self.data = arrow_data(data)
         self.constraintRules: List[ConstraintRule] = []
         self._printStatusUpdates = False
         self._testsetRatio: Optional[float] = None

@@ -86,6 +86,7 @@ class Column:
     nullable: bool = True
     data_bytes: int = 0            # UTF-8 payload bytes (for traffic accounting)
     dictionary: Optional["Dictionary"] = None  # dict_utf8: values = int32 indices into it
+    null_count: Optional[int] = None  # NULL rows, where the constructor knew them (from_pydict, from_arrow)
 
     def view(self) -> L.ColumnView:
         v = L.ColumnView()
@@ -254,6 +255,17 @@ class Table:
                 cols.append(utf8_column(name, b, device=device, large=(dtype == "large_utf8"), nullable=nl))
         return Table(cols)
 
+    @staticmethod
+    def from_arrow(obj, device: str = "cuda") -> "Table":
+        """A pyarrow RecordBatch, Table, RecordBatchReader or sequence of RecordBatches -> ONE device Table (several
+        batches are concatenated), its Columns identical -- values, validity, offsets, padding -- to from_pydict's for
+        the same values.  Arrow types: float64 / float32, int64 / 32 / 16 / 8, bool, date32, timestamp[us], utf8,
+        large_utf8, decimal128(p <= 38, s), dictionary<int8 / 16 / 32 or uint8 / 16, utf8 or large_utf8> (dict_utf8);
+        any other raises TypeError naming the column.  ingest.tables_from_arrow keeps the batches as a chunk list."""
+        from .ingest import table_from_arrow
+
+        return table_from_arrow(obj, device)
+
 
 def column_from_numpy(name: str, dtype: str, values: np.ndarray, valid: Optional[np.ndarray] = None,
                       device: str = "cuda", nullable: bool = True) -> Column:
@@ -283,7 +295,8 @@ def column_from_numpy(name: str, dtype: str, values: np.ndarray, valid: Optional
     bt = None
     if valid is not None and nullable:
         bt = torch.from_numpy(pack_validity(valid)).to(device)
-    return Column(name, dtype, n, vt, bt, None, nullable=nullable and valid is not None)
+    return Column(name, dtype, n, vt, bt, None, nullable=nullable and valid is not None,
+                  null_count=int(n - np.count_nonzero(valid)) if bt is not None else 0)
 
 
 def utf8_column(name: str, values: Sequence[Optional[bytes]], device: str = "cuda", large: bool = False,
@@ -302,7 +315,7 @@ def utf8_column(name: str, values: Sequence[Optional[bytes]], device: str = "cud
     ot = torch.from_numpy(_pad_u8(offs_np.view(np.uint8), 16, 16)).to(device)
     return Column(name, "large_utf8" if large else "utf8", n, torch.from_numpy(raw).to(device),
                   torch.from_numpy(pack_validity(valid)).to(device) if nullable else None, ot,
-                  nullable=nullable, data_bytes=int(offs[-1]))
+                  nullable=nullable, data_bytes=int(offs[-1]), null_count=int(n - valid.sum()) if nullable else 0)
 
 
 def encode_dictionary(values: Iterable) -> Tuple[List[Optional[int]], List]:
@@ -338,4 +351,5 @@ def dict_utf8_column(name: str, indices: Sequence[Optional[int]], dictionary_val
         raise ValueError(f"dictionary index {int(idx[r])} at row {r} is outside the dictionary's {d.n_entries} entries")
     idx[~ok] = 0
     c = column_from_numpy(name, "i32", idx.astype(np.int32), ok, device=device, nullable=nullable)
-    return Column(name, "dict_utf8", c.n_rows, c.values, c.validity, None, nullable=c.nullable, dictionary=d)
+    return Column(name, "dict_utf8", c.n_rows, c.values, c.validity, None, nullable=c.nullable, dictionary=d,
+                  null_count=c.null_count)

@@ -44,7 +44,8 @@ extern "C" {
                                 _mutual_information (self-contained frequency tables) and the row-level results:
                                 dq_row_program_* / dq_row_outcomes (per-row predicate outcomes as bitmaps),
                                 dq_freq_unique_rows (the rows whose group has count 1); arithmetic operands of
-                                predicates: DQ_PRED_EXPR, dq_pred_pool_num_exprs / _expr, dq_expr_eval / _host */
+                                predicates: DQ_PRED_EXPR, dq_pred_pool_num_exprs / _expr, dq_expr_eval / _host; uploads into
+                                caller-owned buffers: dq_upload_to / _payload / _stage */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -307,6 +308,37 @@ dq_status dq_upload_fence(dq_uploader* u, void* hip_stream);
 dq_status dq_upload_release(dq_uploader* u, void* hip_stream);
 dq_status dq_upload_sync(dq_uploader* u);
 void dq_uploader_destroy(dq_uploader* u);
+/* Upload into buffers the caller owns (additions under ABI 6).  dq_upload_to copies one chunk's columns through the
+ * uploader's next pinned slot -- the same CPU threads and the same copy stream as dq_upload -- and DMAs every buffer
+ * to its destination: device memory the caller allocated (one dq_upload_dest per column: the addresses and the WHOLE
+ * sizes of its values / validity / offsets buffers, padding included; a NULL address = the column has no such
+ * buffer).  No device slot is used and nothing is copied on the device afterwards; dq_upload_fence orders a stream
+ * behind the copy as it does for dq_upload, dq_upload_release is not needed (both kinds of upload may share an
+ * uploader).  What arrives is the canonical column image, not the producer's bytes:
+ *   - a NULL row's value is 0, a NULL boolean false, a NULL string empty (bytes under a NULL slot are dropped and the
+ *     offsets rebuilt), a NULL row's dictionary index 0;
+ *   - bitmap bits past the last row are 0; a destination with a validity buffer whose source has none gets all ones;
+ *     a destination without one whose source holds a NULL is DQ_E_INVALID naming column and row;
+ *   - every byte of a destination behind its rows is 0;
+ *   - dictionary indices are widened and range-checked as by dq_upload; a DECIMAL128 value of a valid row with
+ *     |unscaled| >= 10^precision is DQ_E_INVALID naming the column and the first such row (dq_arrow_import and
+ *     dq_upload do not check it).  On an error nothing is uploaded.
+ * dq_upload_payload gives, per column, the value bytes the rows need (a string column: the bytes of its non-NULL rows;
+ * otherwise value_bytes), and checks each column's byte counts and string offsets (ascending, inside the data), so a
+ * caller can size the destinations.  dq_upload_stage is dq_upload_to's host half with no device in it: it writes
+ * every destination's image into `staging` (host memory of staging_bytes) at positions[3 * c + {0 values, 1 validity,
+ * 2 offsets}] (-1: no such buffer; each 256-byte aligned, dests[c]'s sizes long; the destination addresses are only
+ * tested for NULL) and the bytes used to *staged_bytes.  host_threads <= 0: up to 16 CPU threads. */
+typedef struct dq_upload_dest {
+  void* values;
+  void* validity;
+  void* offsets;
+  int64_t value_bytes, validity_bytes, offset_bytes;
+} dq_upload_dest;
+dq_status dq_upload_payload(const dq_host_column* cols, int32_t n_cols, int64_t* value_bytes);
+dq_status dq_upload_stage(const dq_host_column* cols, int32_t n_cols, const dq_upload_dest* dests, void* staging,
+                          int64_t staging_bytes, int32_t host_threads, int64_t* positions, int64_t* staged_bytes);
+dq_status dq_upload_to(dq_uploader* u, const dq_host_column* cols, int32_t n_cols, const dq_upload_dest* dests);
 
 /* The aggregation-result slots of one analyzer (the reference's Row slice at its offset,
  * SURVEY §8b).  has_value[i] = SQL non-null flag of slot i; single-slot analyzers mirror slot 0
