@@ -20,6 +20,7 @@ from .analyzers import (ApproxCountDistinct, Completeness, Compliance, Correlati
 from .lengths import string_lengths  # noqa: F401
 from .grouping import (CountDistinct, Distinctness, Entropy, FrequenciesAndNumRows, Histogram,  # noqa: F401
                        MutualInformation, Uniqueness, UniqueValueRatio)
+from .matching import KeySet, ReferentialIntegrity  # noqa: F401
 from .metrics import (DoubleMetric, Distribution, DistributionValue, Entity, HistogramMetric,  # noqa: F401
                       KeyedDoubleMetric)
 from .profiles import (ColumnProfiler, ColumnProfilerRunBuilder, ColumnProfilerRunner, ColumnProfiles,  # noqa: F401

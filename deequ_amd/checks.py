@@ -20,6 +20,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
 from .analyzers import DataType, DataTypeInstances
 from .grouping import (Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
+from .matching import ReferentialIntegrity
 from .quantiles import ApproxQuantile
 from .runner import AnalysisRunner, AnalyzerContext, arrow_data
 
@@ -286,6 +287,12 @@ class Check:  # Check.scala:59-902
         los, his = _java_double_to_string(lo), _java_double_to_string(hi)
         predicate = f"`{column}` IS NULL OR (`{column}` {left} {los} AND `{column}` {right} {his})"
         return self.satisfies(predicate, f"{column} between {los} and {his}", hint=vals.get("hint"))
+
+    def hasReferentialIntegrity(self, columns, reference, assertion=_is_one, hint=None):
+        """The fraction of rows whose `columns` tuple is a key of `reference` (a matching.KeySet) meets the assertion;
+        a NULL in a key column is not contained.  (Upstream: Check.doesDatasetMatch / ReferentialIntegrity.)"""
+        return self._filterable(lambda w: _named(ReferentialIntegrity(columns, reference, w), assertion,
+                                                 "ReferentialIntegrityConstraint", None, hint))
 
     # ---- constraints on the grouping analyzers and DataType (plain addConstraint: no .where) --------
     def isUnique(self, column, hint=None):  # Check.scala:139-141

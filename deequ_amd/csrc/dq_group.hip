@@ -877,6 +877,86 @@ __global__ __launch_bounds__(256) void unique_rows(GroupCols g, int64_t n, const
     atomicAdd(&tot[1], ng);
   }
 }
+
+// dq_freq_contains_rows: the probe of foreign data, where a key the table lacks is the answer.  The search of the
+// table's ascending keys starts in LDS: contains_splitters takes n_split = min(kSplitters, G) evenly spaced keys once
+// per call (splitter b = keys[b * G / n_split], the first key of bucket b), every workgroup of contains_rows copies
+// them into LDS, a row finds its bucket there (the last splitter <= its key) and finishes in the bucket's
+// ceil(G / n_split) keys in global memory -- log2(G) - 11 dependent global loads instead of log2(G); none when the
+// key is a splitter (every key of a table of at most kSplitters groups is).
+constexpr int kSplitters = 2048;       // 16 KiB of LDS per 256-thread workgroup: 8 workgroups per CU fit in 160 KiB
+constexpr int kContainsMaxGrid = 2048; // workgroups (each reads the splitters once: 32 MiB from L2 at most)
+__global__ void contains_splitters(const uint64_t* __restrict__ keys, int64_t G, int n_split,
+                                   uint64_t* __restrict__ split) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < n_split) split[b] = keys[((int64_t)b * G) / n_split];
+}
+// A wave takes the 64 rows of one output word at a time, as unique_rows.  A row applies when the filter (NULL: every
+// row) has its bit; a row that applies and whose key columns are all non-null computes its key as group_compact does
+// and looks it up.  HASHED: nothing has verified that a found hash is this row's tuple, so the row's tuple is compared
+// by value with the group's stored tuple (row `pos` of the table's store `st`); a different tuple is not contained.
+template <bool HASHED>
+__global__ __launch_bounds__(256) void contains_rows(GroupCols g, GroupCols st, int64_t n,
+                                                     const uint64_t* __restrict__ filter,
+                                                     const uint64_t* __restrict__ keys, int64_t G,
+                                                     const uint64_t* __restrict__ split, int n_split,
+                                                     uint64_t* __restrict__ contained, uint64_t* __restrict__ applies,
+                                                     unsigned long long* __restrict__ tot) {
+  __shared__ uint64_t sp[kSplitters];
+  for (int i = threadIdx.x; i < n_split; i += blockDim.x) sp[i] = split[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t words = (n + 63) >> 6;
+  unsigned long long nc = 0, na = 0;
+  for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < words; w += (int64_t)gridDim.x * 4) {
+    const int64_t r = w * 64 + lane;
+    const bool a = r < n && (!filter || ((filter[w] >> lane) & 1ull));
+    bool found = false;
+    if (a && row_valid(g, r)) {
+      const uint64_t k = HASHED ? tuple_key(g, r) : value_bits(g, 0, r);
+      int b = 0;  // the number of splitters <= k
+      for (int len = n_split; len > 0;) {
+        const int half = len >> 1;
+        if (sp[b + half] <= k) {
+          b += half + 1;
+          len -= half + 1;
+        } else {
+          len = half;
+        }
+      }
+      if (b > 0) {  // (k below the first key, or an empty table: no bucket)
+        --b;
+        int64_t lo = ((int64_t)b * G) / n_split;
+        if (sp[b] != k) {  // the bucket's other keys: lo + 1 .. the next bucket's first key
+          int64_t hi = ((int64_t)(b + 1) * G) / n_split - 1;
+          ++lo;
+          if (lo > hi) {
+            lo = -1;
+          } else {
+            while (lo < hi) {
+              const int64_t mid = (lo + hi) >> 1;
+              if (keys[mid] < k) lo = mid + 1;
+              else hi = mid;
+            }
+            if (keys[lo] != k) lo = -1;
+          }
+        }
+        found = lo >= 0 && (!HASHED || tuple_equal_rows(g, st, r, lo));
+      }
+    }
+    const uint64_t bc = __builtin_amdgcn_ballot_w64(found), ba = __builtin_amdgcn_ballot_w64(a);
+    if (lane == 0) {
+      contained[w] = bc;
+      if (applies) applies[w] = ba;
+      nc += (unsigned long long)__builtin_popcountll(bc);
+      na += (unsigned long long)__builtin_popcountll(ba);
+    }
+  }
+  if (lane == 0 && (nc | na)) {
+    atomicAdd(&tot[0], nc);
+    atomicAdd(&tot[1], na);
+  }
+}
 }  // namespace
 }  // namespace dq
 
@@ -1761,6 +1841,72 @@ dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, cons
   if (h[2]) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: a row whose key is no group of the table (built from other data)");
   if (num_unique) *num_unique = (int64_t)h[0];
   if (num_grouped) *num_grouped = (int64_t)h[1];
+  return DQ_OK;
+}
+
+dq_status dq_freq_contains_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols,
+                                int64_t n_rows, const uint64_t* filter, uint64_t* contained, uint64_t* applies,
+                                void* hip_stream, int64_t* num_contained, int64_t* num_applies) {
+  // the arguments that need no table first, then the table, then what the table says about the columns: all of it
+  // before anything touches the device
+  if (n_rows < 0 || n_rows >= (1ll << 31)) return set_error(DQ_E_INVALID, "dq_freq_contains_rows: 0 <= n_rows < 2^31");
+  if (((uintptr_t)contained & 7) || ((uintptr_t)applies & 7) || ((uintptr_t)filter & 7))
+    return set_error(DQ_E_INVALID, "dq_freq_contains_rows: the bitmaps must be 8-byte aligned device buffers");
+  if (n_rows > 0 && !contained) return set_error(DQ_E_INVALID, "dq_freq_contains_rows: contained is NULL");
+  if (n_rows > 0 && !cols) return set_error(DQ_E_INVALID, "dq_freq_contains_rows: cols is NULL");
+  if (!t) return set_error(DQ_E_INVALID, "dq_freq_contains_rows: table is NULL");
+  if (n_rows == 0) {
+    if (num_contained) *num_contained = 0;
+    if (num_applies) *num_applies = 0;
+    return DQ_OK;
+  }
+  if (t->hashed && !t->has_store)
+    return set_error(DQ_E_STATE, "dq_freq_contains_rows: the table does not own its values (dq_freq_materialize it "
+                                 "first): a found hash is compared with the group's stored tuple");
+  const int n_cols = (int)t->types.size();
+  auto is_str = [](int32_t ty) { return ty == DQ_TYPE_UTF8 || ty == DQ_TYPE_LARGE_UTF8; };
+  std::vector<int32_t> ty(t->types);
+  for (int c = 0; c < n_cols; ++c) {
+    if (types) ty[c] = types[c];
+    // the same type (a decimal's precision and scale are part of its code), or a string column of the other offset
+    // width; nothing is widened
+    if (ty[c] != t->types[c] && !(is_str(ty[c]) && is_str(t->types[c])))
+      return set_error(DQ_E_INVALID, "dq_freq_contains_rows: column %d has type %d, the table's has %d", c, ty[c], t->types[c]);
+    const dq_column_view& v = cols[c];
+    if (!v.values || ((uintptr_t)v.values & 3) || ((uintptr_t)v.validity & 3) || (is_str(ty[c]) && !v.offsets))
+      return set_error(DQ_E_INVALID, "dq_freq_contains_rows: column %d: missing or misaligned buffer", c);
+  }
+  DQ_HIP(hipSetDevice(t->device));
+  const hipStream_t S = reinterpret_cast<hipStream_t>(hip_stream);
+  const GroupCols g = view_cols(ty.data(), n_cols, cols, test_hash_mask(), true);
+  GroupCols st;
+  std::memset(&st, 0, sizeof(st));
+  if (t->hashed) st = store_cols(t);
+  Frame fr(g_arena, t->device);
+  unsigned long long* d_tot = nullptr;
+  uint64_t* d_split = nullptr;
+  if (dq_status s = take(fr, d_tot, 2)) return s;
+  if (dq_status s = take(fr, d_split, kSplitters)) return s;
+  DQ_HIP(hipMemsetAsync(d_tot, 0, 2 * sizeof(unsigned long long), S));
+  const int64_t G = t->n_groups;
+  const int n_split = (int)std::min<int64_t>(kSplitters, G);
+  if (n_split > 0) {
+    hipLaunchKernelGGL(contains_splitters, dim3((n_split + 255) / 256), dim3(256), 0, S, t->d_keys.get(), G, n_split,
+                       d_split);
+    DQ_HIP(hipGetLastError());
+  }
+  const int64_t words = (n_rows + 63) / 64;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(kContainsMaxGrid, (words + 3) / 4));
+  with_bool(t->hashed != 0, [&](auto hashed) {
+    hipLaunchKernelGGL(contains_rows<decltype(hashed)::value>, dim3(grid), dim3(256), 0, S, g, st, n_rows, filter,
+                       t->d_keys.get(), G, d_split, n_split, contained, applies, d_tot);
+  });
+  DQ_HIP(hipGetLastError());
+  unsigned long long h[2];
+  DQ_HIP(hipMemcpyAsync(h, d_tot, sizeof(h), hipMemcpyDeviceToHost, S));
+  DQ_HIP(hipStreamSynchronize(S));
+  if (num_contained) *num_contained = (int64_t)h[0];
+  if (num_applies) *num_applies = (int64_t)h[1];
   return DQ_OK;
 }
 

@@ -24,6 +24,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
                         Mean, MinLength, Minimum, PatternMatch, Size, StandardDeviation, Sum)
 from .grouping import (CountDistinct, Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
+from .matching import ReferentialIntegrity, StoredKeySet
 from .metrics import (Distribution, DistributionValue, DoubleMetric, Entity, Failure, HistogramMetric,
                       KeyedDoubleMetric, MetricCalculationRuntimeException, Success)
 from .quantiles import ApproxQuantile, ApproxQuantiles
@@ -368,6 +369,11 @@ def serialize_analyzer(analyzer: Analyzer) -> dict:  # AnalyzerSerializer (Analy
         return {"analyzerName": "ApproxQuantiles", "column": analyzer.column,
                 "quantiles": ",".join(_java_double_to_string(q) for q in analyzer.quantiles),
                 "relativeError": analyzer.relativeError}
+    if t is ReferentialIntegrity:
+        # (no upstream layout: the analyzer postdates the serde this follows.)  The key set itself is not stored,
+        # only its size: the analyzer comes back able to key stored metrics and refusing to run (StoredKeySet)
+        return {"analyzerName": "ReferentialIntegrity", "columns": list(analyzer.columns), "where": analyzer.where,
+                "numKeys": int(analyzer.reference.num_keys)}
     raise ValueError(f"Unable to serialize analyzer {analyzer}.")
 
 
@@ -395,6 +401,8 @@ def deserialize_analyzer(node: dict) -> Analyzer:  # AnalyzerDeserializer (:349-
     if name == "ApproxQuantiles":
         return ApproxQuantiles(node["column"], [float(q) for q in node["quantiles"].split(",")],
                                float(node["relativeError"]))
+    if name == "ReferentialIntegrity":
+        return ReferentialIntegrity(list(node["columns"]), StoredKeySet(int(node["numKeys"])), where)
     raise ValueError(f"Unable to deserialize analyzer {name}.")
 
 

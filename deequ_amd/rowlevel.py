@@ -9,9 +9,11 @@ upstream: a row passes when the thing the metric counts holds for it.
   Compliance (satisfies, ...)       the predicate is TRUE (NULL is not a pass)
   PatternMatch (hasPattern, ...)    regexp_extract(col, pattern, 0) != '' (a NULL value fails, as the metric counts it)
   Uniqueness (isUnique, ...)        the row's group has count 1 (a NULL key column: not unique)
+  ReferentialIntegrity              the row's tuple is a key of the reference key set (a NULL key column: not contained)
 
 The first three run as row programs (dq_row_program_create / dq_row_outcomes: the predicate pass that stores rows
-instead of counting them); Uniqueness probes the grouping's frequency table (dq_freq_unique_rows).  Every other
+instead of counting them); Uniqueness probes the grouping's frequency table (dq_freq_unique_rows) and
+ReferentialIntegrity the reference's key set (dq_freq_contains_rows, its `where` bitmap as the filter).  Every other
 constraint has no row-level form and is listed in `skipped` with the reason; for a check's AND it counts as passing.
 A predicate outside the GPU grammar is skipped the same way, with the compiler's reason -- never dropped silently.
 
@@ -33,6 +35,7 @@ import numpy as np
 from . import _lib as L
 from .analyzers import Completeness, Compliance, PatternMatch, PlanBuilder
 from .grouping import Uniqueness, _gpu_type, build_frequencies
+from .matching import ReferentialIntegrity
 from .metrics import NoSuchColumnException
 from .predicates import UnsupportedPredicate
 from .table import Table, plain_utf8
@@ -48,12 +51,14 @@ def max_outputs() -> int:
 @dataclass(frozen=True)
 class RowForm:
     """The row-level form of one constraint.  kind "predicate": pred = ("sql", text) or ("regex", column, pattern),
-    where = the `where` text or None.  kind "unique": columns = the grouping columns."""
+    where = the `where` text or None.  kind "unique": columns = the grouping columns.  kind "contains": analyzer =
+    the ReferentialIntegrity analyzer (its columns, key set and `where`)."""
     key: str
     kind: str
     pred: Optional[tuple] = None
     where: Optional[str] = None
     columns: Tuple[str, ...] = ()
+    analyzer: object = None
 
     def roots(self) -> List[tuple]:
         return [self.pred] + ([("sql", self.where)] if self.where is not None else [])
@@ -80,6 +85,8 @@ def row_form(constraint) -> Union[RowForm, str]:
         return RowForm(key, "predicate", ("sql", analyzer.predicate), analyzer.where)
     if isinstance(analyzer, Uniqueness):
         return RowForm(key, "unique", columns=tuple(analyzer.groupingColumns()))
+    if isinstance(analyzer, ReferentialIntegrity):
+        return RowForm(key, "contains", where=analyzer.where, columns=tuple(analyzer.columns), analyzer=analyzer)
     return f"{type(analyzer).__name__} has no row-level form"
 
 
@@ -237,8 +244,12 @@ def _sql_texts(checks) -> List[str]:
     for check in checks:
         for c in check.constraints:
             f = row_form(c)
-            if not isinstance(f, str) and f.kind == "predicate":
+            if isinstance(f, str):
+                continue
+            if f.kind == "predicate":
                 out += [r[1] for r in f.roots() if r[0] == "sql"]
+            elif f.kind == "contains" and f.where is not None:
+                out.append(f.where)
     return list(dict.fromkeys(out))
 
 
@@ -271,6 +282,22 @@ def plan_row_level(checks, schema, max_outputs_per_program: Optional[int] = None
                     if missing:
                         skipped.append((key, f"NoSuchColumnException: Input data does not include column {missing[0]}!"))
                         continue
+                elif f.kind == "contains":
+                    from .analyzers import Preconditions
+
+                    err = Preconditions.findFirstFailing(schema, f.analyzer.preconditions())
+                    if err is not None:
+                        skipped.append((key, f"{type(err).__name__}: {err}"))
+                        continue
+                    if f.where is not None:  # its `where` runs as a row program of its own (predicate_bitmaps)
+                        try:
+                            RowProgram([RowForm(key, "predicate", ("sql", f.where))], schema, expr_columns).close()
+                        except UnsupportedPredicate as e:
+                            skipped.append((key, f"UnsupportedPredicate: {e}"))
+                            continue
+                        except NoSuchColumnException as e:
+                            skipped.append((key, f"NoSuchColumnException: {e}"))
+                            continue
                 else:
                     try:  # alone first: what the GPU grammar (or the device stack) does not take is skipped, with the reason
                         RowProgram([f], schema, expr_columns).close()
@@ -457,6 +484,64 @@ def _unique_outcome(form: RowForm, chunks: List[Table]) -> RowOutcome:
     return RowOutcome(form.key, out)
 
 
+def _filtered_outcome(p, a, npass: int, napp: int, n: int, null_mode: bool) -> ChunkOutcome:
+    """One chunk's outcome from a pass bitmap p and the `where` bitmap a (None: no `where`)."""
+    if a is None:
+        return ChunkOutcome(p, None, npass, n, n)
+    if null_mode:
+        return ChunkOutcome(p, a, npass, n, napp)
+    # a filtered row passes
+    b = (_words(p) | (~_words(a) & _words(_row_mask(n, p.device)))).view(p.dtype)
+    return ChunkOutcome(b, None, npass + (n - napp), n, n)
+
+
+def _contains_outcome(form: RowForm, chunks: List[Table], null_mode: bool) -> RowOutcome:
+    """pass = contained, applies = the `where` bitmap: one dq_freq_contains_rows per chunk."""
+    res = form.analyzer.probe(chunks, want_applies=form.where is not None)
+    return RowOutcome(form.key, [_filtered_outcome(*r, t.num_rows, null_mode) for t, r in zip(chunks, res)])
+
+
+def _prepared(chunks: List[Table], texts: Sequence[str], compile):
+    """(the chunks as row programs over `texts` read them, what `compile` made of them).  The derived columns of the
+    texts' arithmetic operands are attached -- one per distinct expression, once per chunk, on tables of this call's
+    own (outcomes and row takes refer to the caller's chunks) -- then compile(schema, expr_columns) -> (compiled, its
+    RowPrograms) runs, and the dictionary-encoded columns the programs touch are replaced by their decoded columns;
+    where that changes a column's type (large_utf8 entries) the programs are closed and compiled again."""
+    from .expressions import attach_expression_columns, text_expressions
+
+    pred_chunks, failed = attach_expression_columns(chunks, text_expressions(texts, chunks[0].schema))
+    if failed:
+        raise next(iter(failed.values()))
+    compiled, programs = compile(pred_chunks[0].schema, pred_chunks[0].expr_columns)
+    touched = {c for prog in programs for c in prog.columns}
+    dict_cols = {n for n, dt, _ in chunks[0].schema if dt == "dict_utf8"} & touched
+    if dict_cols:
+        before = _plain_schema(pred_chunks[0].schema)
+        pred_chunks = plain_utf8(pred_chunks, dict_cols)
+        if before != list(pred_chunks[0].schema):  # (large_utf8 entries)
+            for prog in programs:
+                prog.close()
+            compiled, programs = compile(pred_chunks[0].schema, pred_chunks[0].expr_columns)
+    return pred_chunks, compiled
+
+
+def predicate_bitmaps(chunks: List[Table], text: str) -> list:
+    """Per chunk the bitmap of the rows for which the SQL predicate `text` is TRUE: a one-output row program, its
+    arithmetic operands and dictionary columns handled as row_level_results handles them (_prepared).  A text outside
+    the GPU grammar raises UnsupportedPredicate."""
+    form = RowForm(text, "predicate", ("sql", text))
+
+    def compile_one(schema, expr_columns):
+        prog = RowProgram([form], _plain_schema(schema), expr_columns)
+        return prog, [prog]
+
+    pred_chunks, prog = _prepared(chunks, [text], compile_one)
+    try:
+        return [prog.evaluate(t, [False])[0][0] for t in pred_chunks]
+    finally:
+        prog.close()
+
+
 def row_level_results(checks, data, filteredRow: str = "TRUE") -> RowLevelResults:
     """Per-row outcomes of the checks' constraints over `data` (a Table or a list of chunk Tables)."""
     if filteredRow not in FILTERED_ROW:
@@ -468,24 +553,11 @@ def row_level_results(checks, data, filteredRow: str = "TRUE") -> RowLevelResult
     chunks = [data] if isinstance(data, Table) else list(data)
     if not chunks:
         raise ValueError("row_level_results: no chunks")
-    # the derived columns of the predicates' arithmetic operands: one per distinct expression, once per chunk, on
-    # tables of this call's own (the outcomes and the row takes refer to the caller's chunks)
-    from .expressions import attach_expression_columns, text_expressions
+    def compile_plan(schema, expr_columns):
+        plan = plan_row_level(checks, schema, expr_columns=expr_columns)
+        return plan, plan.programs
 
-    pred_chunks, failed = attach_expression_columns(chunks, text_expressions(_sql_texts(checks), chunks[0].schema))
-    if failed:
-        raise next(iter(failed.values()))
-    plan = plan_row_level(checks, pred_chunks[0].schema, expr_columns=pred_chunks[0].expr_columns)
-    # the dictionary-encoded columns a predicate or pattern touches: read through their decoded columns
-    touched = {c for prog in plan.programs for c in prog.columns}
-    dict_cols = {n for n, dt, _ in chunks[0].schema if dt == "dict_utf8"} & touched
-    if dict_cols:
-        before = _plain_schema(pred_chunks[0].schema)
-        pred_chunks = plain_utf8(pred_chunks, dict_cols)
-        if before != list(pred_chunks[0].schema):  # (large_utf8 entries)
-            for prog in plan.programs:
-                prog.close()
-            plan = plan_row_level(checks, pred_chunks[0].schema, expr_columns=pred_chunks[0].expr_columns)
+    pred_chunks, plan = _prepared(chunks, _sql_texts(checks), compile_plan)
     null_mode = filteredRow == "NULL"
     constraints: Dict[str, RowOutcome] = {}
     try:
@@ -495,15 +567,7 @@ def row_level_results(checks, data, filteredRow: str = "TRUE") -> RowLevelResult
             for i, f in enumerate(prog.forms):
                 outs = []
                 for t, res in zip(pred_chunks, per_chunk):
-                    p, a, npass, napp = res[i]
-                    n = t.num_rows
-                    if a is None:
-                        outs.append(ChunkOutcome(p, None, npass, n, n))
-                    elif null_mode:
-                        outs.append(ChunkOutcome(p, a, npass, n, napp))
-                    else:  # a filtered row passes
-                        b = (_words(p) | (~_words(a) & _words(_row_mask(n, p.device)))).view(p.dtype)
-                        outs.append(ChunkOutcome(b, None, npass + (n - napp), n, n))
+                    outs.append(_filtered_outcome(*res[i], t.num_rows, null_mode))
                 constraints[f.key] = RowOutcome(f.key, outs)
     finally:
         for prog in plan.programs:
@@ -511,5 +575,7 @@ def row_level_results(checks, data, filteredRow: str = "TRUE") -> RowLevelResult
     for key, f in plan.forms.items():
         if f.kind == "unique":
             constraints[key] = _unique_outcome(f, chunks)
+        elif f.kind == "contains":
+            constraints[key] = _contains_outcome(f, pred_chunks, null_mode)  # (its `where`'s derived columns)
     per_check = {desc: _and_outcomes(desc, [constraints[k] for k in keys], chunks) for desc, keys in plan.checks}
     return RowLevelResults(data, filteredRow, constraints, per_check, list(plan.skipped), plan)

@@ -45,7 +45,8 @@ extern "C" {
                                 dq_row_program_* / dq_row_outcomes (per-row predicate outcomes as bitmaps),
                                 dq_freq_unique_rows (the rows whose group has count 1); arithmetic operands of
                                 predicates: DQ_PRED_EXPR, dq_pred_pool_num_exprs / _expr, dq_expr_eval / _host; uploads into
-                                caller-owned buffers: dq_upload_to / _payload / _stage */
+                                caller-owned buffers: dq_upload_to / _payload / _stage; referential integrity:
+                                dq_freq_contains_rows (the rows whose tuple is a group of another table's key set) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -860,6 +861,31 @@ dq_status dq_row_outcomes(dq_row_program* prog, const dq_column_view* cols, int6
 dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols, int64_t n_rows,
                               uint64_t* unique, uint64_t* grouped, void* hip_stream, int64_t* num_unique,
                               int64_t* num_grouped);
+/* Referential integrity: the rows of one chunk whose tuple over the key columns C is a group of the frequency table
+ * t, a key set built from OTHER data (dq_freq_build of the reference table's columns, then dq_freq_materialize) --
+ * SQL's `C IN (SELECT keys)` / a left semi-join, per row.  A key the table lacks is the answer here, never an error.
+ * cols: the chunk's views of C in the table's column order (the table's arity is the number of views read); types:
+ * their type codes, or NULL for the table's own.  A string column may have the other offset width, as in
+ * dq_freq_unique_rows; any other difference -- a decimal of another precision or scale included -- is DQ_E_INVALID
+ * naming the column and both type codes.  Nothing is widened implicitly: an i32 column is never matched against i64
+ * keys; cast it first.
+ * filter (NULL: every row): a bitmap in the layout above, the rows to look at (a `where`).
+ * contained: bit r = 1 iff filter is NULL or has bit r set, AND every column of C is non-null in row r, AND the
+ * row's tuple is a group of t.  A NULL in any key column is "not contained" (SQL IN / semi-join: NULL matches
+ * nothing) and the row still counts in the denominator.  applies (NULL: not wanted): bit r = 1 iff filter is NULL or
+ * has bit r set.  Bitmap layout, zero tail bits, 8-byte alignment (filter too), n_rows = 0 (DQ_OK, nothing written),
+ * the n_rows < 2^31 limit and the synchronisation of hip_stream are dq_freq_unique_rows's; *num_contained /
+ * *num_applies (host, optional) are the set bits.  The table's counts are ignored: only membership matters.
+ * An unhashed table (one fixed-width column): membership is equality of the grouping's value bits -- NaN canonical,
+ * -0.0 and 0.0 distinct.  A hashed table (strings, decimals, several columns) must be self-contained
+ * (dq_freq_self_contained), else DQ_E_STATE: nothing has verified that a found hash is the row's tuple, so the row is
+ * contained only if its tuple equals the group's stored tuple column by column (string bytes and length, a decimal's
+ * 16 bytes, value bits otherwise); a found hash with a different tuple is "not contained", never the collision
+ * error.  Arguments are checked before anything is launched: n_rows, the bitmaps' alignment, NULL contained / cols /
+ * table, the table's state, the types, the views' buffers. */
+dq_status dq_freq_contains_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols,
+                                int64_t n_rows, const uint64_t* filter, uint64_t* contained, uint64_t* applies,
+                                void* hip_stream, int64_t* num_contained, int64_t* num_applies);
 /* Row-level random split (the train / test split of suggestions/ConstraintSuggestionRunner.scala:127-148).  Row r of
  * the chunk has the global index g = row0 + r; h = XXH64 of g's 8 little-endian bytes under `seed`,
  * u = (h >> 11) * 2^-53, and the row is a test row iff u < test_ratio, else a training row: a pure function of
