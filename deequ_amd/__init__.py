@@ -17,6 +17,7 @@ from .repository import (AnalysisResult, AnalysisResultSerde, FileSystemMetricsR
 from .analyzers import (ApproxCountDistinct, Completeness, Compliance, Correlation, DataType,  # noqa: F401
                         DataTypeInstances, MaxLength, Maximum, Mean, MinLength, Minimum, PatternMatch, Patterns, Size,
                         StandardDeviation, Sum)
+from .binning import Bins  # noqa: F401
 from .lengths import string_lengths  # noqa: F401
 from .grouping import (CountDistinct, Distinctness, Entropy, FrequenciesAndNumRows, Histogram,  # noqa: F401
                        MutualInformation, Uniqueness, UniqueValueRatio)

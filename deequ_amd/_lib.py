@@ -425,6 +425,12 @@ def _load():
     L.dq_freq_build_weighted.restype = c.c_int32
     L.dq_freq_build_weighted.argtypes = [P(c.c_int32), c.c_int32, P(ColumnView), P(c.c_int64), P(c.c_void_p), c.c_int32,
                                          c.c_int32, c.c_void_p, P(c.c_void_p)]
+    L.dq_bins_create.restype = c.c_int32
+    L.dq_bins_create.argtypes = [P(c.c_double), c.c_int32, c.c_int32, P(c.c_void_p)]
+    L.dq_bins_destroy.restype = None
+    L.dq_bins_destroy.argtypes = [c.c_void_p]
+    L.dq_bin_count.restype = c.c_int32
+    L.dq_bin_count.argtypes = [c.c_void_p, c.c_int32, P(ColumnView), c.c_int64, c.c_void_p, c.c_int32, c.c_void_p]
     L.dq_dict_check_indices.restype = c.c_int32
     L.dq_dict_check_indices.argtypes = [c.c_int32, c.c_void_p, c.c_int64, c.c_void_p, c.c_int32, c.c_int64, c.c_void_p]
     L.dq_arrow_import_dictionary.restype = c.c_int32
@@ -462,7 +468,7 @@ EXPORTED = [
     "dq_schema_plan_create", "dq_schema_plan_destroy", "dq_schema_validate", "dq_schema_check_host",
     "dq_take_index", "dq_take_rows", "dq_split_rows", "dq_split_rows_host",
     "dq_dict_entries", "dq_dict_decode", "dq_dict_check_indices", "dq_arrow_import_dictionary",
-    "dq_dict_count", "dq_freq_build_weighted",
+    "dq_dict_count", "dq_freq_build_weighted", "dq_bins_create", "dq_bins_destroy", "dq_bin_count",
     "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
     "dq_row_max_outputs", "dq_row_program_create", "dq_row_program_info", "dq_row_program_destroy", "dq_row_outcomes",
     "dq_freq_unique_rows", "dq_freq_contains_rows",

@@ -314,14 +314,15 @@ class Check:  # Check.scala:59-902
                                                   f"UniqueValueRatioConstraint({a}"))
 
     def hasNumberOfDistinctValues(self, column, assertion, binningUdf=None, maxBins=Histogram.MaximumAllowedDetailBins,
-                                  hint=None):  # Check.scala:269-278, histogramBinConstraint (Constraint.scala:133-147)
-        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins), assertion, "HistogramBinConstraint",
-                                         lambda d: d.numberOfBins, hint))
+                                  hint=None, *, binning=None):
+        # Check.scala:269-278, histogramBinConstraint (Constraint.scala:133-147); binning: a binning.Bins
+        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins, binning), assertion,
+                                         "HistogramBinConstraint", lambda d: d.numberOfBins, hint))
 
     def hasHistogramValues(self, column, assertion, binningUdf=None, maxBins=Histogram.MaximumAllowedDetailBins,
-                           hint=None):  # Check.scala:295-304
-        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins), assertion, "HistogramConstraint",
-                                         None, hint))
+                           hint=None, *, binning=None):  # Check.scala:295-304; binning: a binning.Bins
+        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins, binning), assertion,
+                                         "HistogramConstraint", None, hint))
 
     def hasEntropy(self, column, assertion, hint=None):  # Check.scala:353-360
         return self.addConstraint(_named(Entropy(column), assertion, "EntropyConstraint", None, hint))

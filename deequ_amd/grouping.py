@@ -512,23 +512,39 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
     """Counts of the column's values cast to string (NULL -> "NullValue"): the maxDetailBins largest
     groups (ties in key order; Spark's rdd.top leaves them unspecified) with ratio count / numRows, and
     the number of bins.  The frequencies are the device table of build_frequencies; values are
-    rendered on the host only for the returned bins."""
+    rendered on the host only for the returned bins.
+
+    binning: a binning.Bins, the declarative stand-in for binningUdf (which runs in Spark, not here).  The numeric
+    column is counted into the declared bins in one device pass (dq_bin_count) and the groups are the bins' labels,
+    as Spark's groupBy over a UDF returning those labels builds them: a bin no row fell into makes no group, so
+    numberOfBins counts the non-empty bins (and "NullValue").  The binning is part of str(analyzer), which names the
+    persisted state: two binnings of one column never share a state.  The state's keys are plain strings, so merging
+    states that were built with different bins cannot be detected: it is the caller's error."""
     name = "Histogram"
     grouping = True
     direct = True
     NullFieldReplacement = "NullValue"
     MaximumAllowedDetailBins = 1000
 
-    def __init__(self, column: str, binningUdf=None, maxDetailBins: int = 1000):
+    def __init__(self, column: str, binningUdf=None, maxDetailBins: int = 1000, binning=None):
+        from .binning import Bins
+
+        if binning is not None and not isinstance(binning, Bins):
+            raise TypeError(f"binning: a Bins is needed (Bins.edges / Bins.equal_width), got {type(binning).__name__}")
         self.column = column
         self.binningUdf = binningUdf
         self.maxDetailBins = maxDetailBins
+        self.binning = binning
 
     def _fields(self):
-        return (self.column, id(self.binningUdf) if self.binningUdf is not None else None, self.maxDetailBins)
+        base = (self.column, id(self.binningUdf) if self.binningUdf is not None else None, self.maxDetailBins)
+        return base if self.binning is None else base + (self.binning,)
 
     def __str__(self):
-        return f"Histogram({self.column},{'None' if self.binningUdf is None else 'Some(udf)'},{self.maxDetailBins})"
+        udf = "None" if self.binningUdf is None else "Some(udf)"
+        if self.binning is not None:
+            return f"Histogram({self.column},{udf},{self.maxDetailBins},{self.binning})"
+        return f"Histogram({self.column},{udf},{self.maxDetailBins})"
 
     __repr__ = __str__
 
@@ -546,6 +562,11 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
             if self.maxDetailBins > Histogram.MaximumAllowedDetailBins:
                 raise IllegalAnalyzerParameterException(
                     f"Cannot return histogram values for more than {Histogram.MaximumAllowedDetailBins} values")
+            if self.binningUdf is not None and self.binning is not None:
+                raise IllegalAnalyzerParameterException(
+                    "Histogram takes a binningUdf or a binning, not both")
+        if self.binning is not None:  # the bins are over numbers: the reference's wrong-column-type failure
+            return [param_check, Preconditions.hasColumn(self.column), Preconditions.isNumeric(self.column)]
         return [param_check, Preconditions.hasColumn(self.column)]
 
     def toFailureMetric(self, e: BaseException):
@@ -629,7 +650,13 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
                 from .metrics import UnsupportedOnGpuPathException
 
                 raise UnsupportedOnGpuPathException(f"{self}: a binning UDF runs in Spark, not on the GPU path")
-            state = build_frequencies(data, [self.column])
+            if self.binning is not None:
+                from .binning import binned_frequencies
+                from .runner import _chunks
+
+                state = binned_frequencies(_chunks(data), self.column, self.binning)
+            else:
+                state = build_frequencies(data, [self.column])
             if aggregateWith is not None or saveStatesWith is not None:
                 state.materialize()  # once, before the merge and the first persist
             if aggregateWith is not None:

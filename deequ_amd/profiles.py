@@ -55,6 +55,9 @@ class NumericColumnProfile:  # ColumnProfile.scala:44-58
     sum: Optional[float]
     stdDev: Optional[float]
     approxPercentiles: Optional[List[float]]
+    # the equal-width distribution between minimum and maximum (withNumericDistributions; None: not asked for, or the
+    # column has no finite minimum < maximum)
+    distribution: Optional[Distribution] = None
 
 
 ColumnProfile = Union[StandardColumnProfile, NumericColumnProfile]
@@ -85,6 +88,9 @@ class ColumnProfiles:  # ColumnProfile.scala:60-62
                     if v is not None:
                         c[key] = v
                 c["approxPercentiles"] = list(p.approxPercentiles or [])
+                if p.distribution is not None:
+                    c["distribution"] = [{"value": k, "count": v.absolute, "ratio": v.ratio}
+                                         for k, v in p.distribution.values.items()]
             columns.append(c)
         return json.dumps({"columns": columns}, indent=2)
 
@@ -311,8 +317,35 @@ def compute_histograms(data, columns: Sequence[str]) -> Dict[str, Distribution]:
     return {c: out[c] for c in requested}
 
 
+def numeric_distributions(data, numeric: NumericColumnStatistics, columns: Sequence[str],
+                          numberOfBuckets: int) -> Dict[str, Distribution]:
+    """Per numeric column with a finite minimum < maximum: the Distribution of Histogram(column, binning =
+    Bins.equal_width(minimum, maximum, numberOfBuckets)) over `data`, the columns pass 2 read (a numeric string column:
+    its cast).  Every non-NULL value lies between the two, so the slots below and above stay empty; a column whose
+    histogram fails is left out."""
+    import math
+
+    from .binning import Bins
+    from .grouping import Histogram
+
+    out: Dict[str, Distribution] = {}
+    for name in columns:
+        lo, hi = numeric.minima.get(name), numeric.maxima.get(name)
+        if lo is None or hi is None or not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+            continue
+        try:
+            bins = Bins.equal_width(lo, hi, numberOfBuckets)
+        except ValueError:  # (the range is too narrow for that many distinct edges)
+            continue
+        metric = Histogram(name, binning=bins).calculate(data)
+        if metric.value.isSuccess:
+            out[name] = metric.value.get()
+    return out
+
+
 def create_profiles(columns: Sequence[str], generic: GenericColumnStatistics, numeric: NumericColumnStatistics,
-                    histograms: Dict[str, Distribution]) -> ColumnProfiles:
+                    histograms: Dict[str, Distribution],
+                    distributions: Optional[Dict[str, Distribution]] = None) -> ColumnProfiles:
     """createProfiles (:617-670)."""
     profiles: Dict[str, ColumnProfile] = {}
     I = DataTypeInstances
@@ -322,7 +355,8 @@ def create_profiles(columns: Sequence[str], generic: GenericColumnStatistics, nu
         if generic.typeOf(name) in (I.Integral, I.Fractional):
             profiles[name] = NumericColumnProfile(*common, numeric.means.get(name), numeric.maxima.get(name),
                                                   numeric.minima.get(name), numeric.sums.get(name),
-                                                  numeric.stdDevs.get(name), numeric.approxPercentiles.get(name))
+                                                  numeric.stdDevs.get(name), numeric.approxPercentiles.get(name),
+                                                  (distributions or {}).get(name))
         else:
             profiles[name] = StandardColumnProfile(*common)
     return ColumnProfiles(profiles, generic.numRecords)
@@ -335,7 +369,16 @@ class ColumnProfiler:  # ColumnProfiler.scala:66-188
     def profile(data, restrictToColumns: Optional[Sequence[str]] = None, printStatusUpdates: bool = False,
                 lowCardinalityHistogramThreshold: int = DEFAULT_CARDINALITY_THRESHOLD, metricsRepository=None,
                 reuseExistingResultsUsingKey=None, failIfResultsForReusingMissing: bool = False,
-                saveInMetricsRepositoryUsingKey=None) -> ColumnProfiles:
+                saveInMetricsRepositoryUsingKey=None,
+                numericDistributionBuckets: Optional[int] = None) -> ColumnProfiles:
+        """numericDistributionBuckets (ColumnProfilerRunBuilder.withNumericDistributions; None: off): every numeric
+        column with a finite minimum < maximum also gets `distribution`, that many equal-width bins between the two."""
+        if numericDistributionBuckets is not None:
+            from .binning import MAX_BINS
+
+            if (not isinstance(numericDistributionBuckets, int) or isinstance(numericDistributionBuckets, bool)
+                    or not 1 <= numericDistributionBuckets <= MAX_BINS):
+                raise ValueError(f"numberOfBuckets = {numericDistributionBuckets!r}: an integer in 1..{MAX_BINS} is needed")
         if (metricsRepository is not None or reuseExistingResultsUsingKey is not None or failIfResultsForReusingMissing
                 or saveInMetricsRepositoryUsingKey is not None):
             raise NotImplementedError("ColumnProfiler.profile: the metrics repository is not part of the GPU path")
@@ -361,17 +404,20 @@ class ColumnProfiler:  # ColumnProfiler.scala:66-188
         I = DataTypeInstances
         numeric_columns = [n for n in relevant if generic.typeOf(n) in (I.Integral, I.Fractional)]
         numeric = NumericColumnStatistics({}, {}, {}, {}, {}, {})
+        distributions: Dict[str, Distribution] = {}
         if numeric_columns:
             # castNumericStringColumns: the string columns among them become i64 / f64; native ones are read as they are
             casted = cast_numeric_string_columns(data, {n: generic.typeOf(n) for n in numeric_columns})
             second = AnalysisRunner.onData(casted).addAnalyzers(second_pass_analyzers(numeric_columns)).run()
             numeric = extract_numeric_statistics(second)
+            if numericDistributionBuckets is not None:
+                distributions = numeric_distributions(casted, numeric, numeric_columns, numericDistributionBuckets)
 
         if printStatusUpdates:
             print("### PROFILING: Computing histograms of low-cardinality columns in pass (3/3)...")
         targets = find_target_columns_for_histograms(schema, generic, lowCardinalityHistogramThreshold)
         histograms = compute_histograms(data, targets) if targets else {}
-        return create_profiles(relevant, generic, numeric, histograms)
+        return create_profiles(relevant, generic, numeric, histograms, distributions)
 
 
 class ColumnProfilerRunner:  # profiles/ColumnProfilerRunner.scala:42-48
@@ -385,6 +431,7 @@ class ColumnProfilerRunBuilder:  # profiles/ColumnProfilerRunBuilder.scala:27-10
         self._restrictToColumns: Optional[Sequence[str]] = None
         self._printStatusUpdates = False
         self._threshold = DEFAULT_CARDINALITY_THRESHOLD
+        self._distribution_buckets: Optional[int] = None
 
     def restrictToColumns(self, columns: Sequence[str]) -> "ColumnProfilerRunBuilder":
         self._restrictToColumns = list(columns)
@@ -398,7 +445,14 @@ class ColumnProfilerRunBuilder:  # profiles/ColumnProfilerRunBuilder.scala:27-10
         self._threshold = threshold
         return self
 
+    def withNumericDistributions(self, numberOfBuckets: int = 100) -> "ColumnProfilerRunBuilder":
+        """Opt in (default off): NumericColumnProfile.distribution, numberOfBuckets equal-width bins between a numeric
+        column's minimum and maximum, counted in one device pass per column (Histogram's `binning`)."""
+        self._distribution_buckets = numberOfBuckets
+        return self
+
     def run(self) -> ColumnProfiles:
         return ColumnProfiler.profile(self.data, restrictToColumns=self._restrictToColumns,
                                       printStatusUpdates=self._printStatusUpdates,
-                                      lowCardinalityHistogramThreshold=self._threshold)
+                                      lowCardinalityHistogramThreshold=self._threshold,
+                                      numericDistributionBuckets=self._distribution_buckets)

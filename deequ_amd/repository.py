@@ -358,7 +358,12 @@ def serialize_analyzer(analyzer: Analyzer) -> dict:  # AnalyzerSerializer (Analy
     if t is Histogram:
         if analyzer.binningUdf is not None:
             raise ValueError("Unable to serialize Histogram with binningUdf!")
-        return {"analyzerName": "Histogram", "column": analyzer.column, "maxDetailBins": int(analyzer.maxDetailBins)}
+        node = {"analyzerName": "Histogram", "column": analyzer.column, "maxDetailBins": int(analyzer.maxDetailBins)}
+        if analyzer.binning is not None:  # (no upstream layout; without a binning the JSON is the reference's)
+            from .binning import bins_to_json
+
+            node["binning"] = bins_to_json(analyzer.binning)
+        return node
     if t is Correlation:
         return {"analyzerName": "Correlation", "firstColumn": analyzer.firstColumn,
                 "secondColumn": analyzer.secondColumn, "where": analyzer.where}
@@ -393,7 +398,12 @@ def deserialize_analyzer(node: dict) -> Analyzer:  # AnalyzerDeserializer (:349-
     if name in _COLUMNS_ANALYZERS:
         return _COLUMNS_ANALYZERS[name](list(node["columns"]))
     if name == "Histogram":
-        return Histogram(node["column"], None, int(node["maxDetailBins"]))
+        binning = None
+        if node.get("binning") is not None:
+            from .binning import bins_from_json
+
+            binning = bins_from_json(node["binning"])
+        return Histogram(node["column"], None, int(node["maxDetailBins"]), binning)
     if name == "Correlation":
         return Correlation(node["firstColumn"], node["secondColumn"], where)
     if name == "ApproxQuantile":

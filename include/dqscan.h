@@ -46,7 +46,8 @@ extern "C" {
                                 dq_freq_unique_rows (the rows whose group has count 1); arithmetic operands of
                                 predicates: DQ_PRED_EXPR, dq_pred_pool_num_exprs / _expr, dq_expr_eval / _host; uploads into
                                 caller-owned buffers: dq_upload_to / _payload / _stage; referential integrity:
-                                dq_freq_contains_rows (the rows whose tuple is a group of another table's key set) */
+                                dq_freq_contains_rows (the rows whose tuple is a group of another table's key set);
+                                binned histograms: dq_bins_create / _destroy, dq_bin_count */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -222,6 +223,37 @@ dq_status dq_dict_decode(int32_t dict_type, const dq_column_view* dict, int64_t 
                          const dq_column_view* indices, int64_t n_rows, void* out_values, int64_t values_capacity,
                          uint8_t* out_validity, void* out_offsets, int64_t* data_bytes, int32_t device,
                          void* hip_stream);
+
+/* ---- Binned histograms: a numeric column counted into declared bins (additions under ABI 6) ----
+ * dq_bins_create: edges (host): n_edges = k + 1 finite, strictly increasing binary64 numbers giving k bins,
+ * 1 <= k <= 4096; the handle keeps a device copy of them on `device`.  Fewer than 2 edges, a non-finite edge
+ * ("edges[i] is not finite") or one not above its predecessor ("edges[i] is not greater than edges[i-1]") is
+ * DQ_E_INVALID; more than 4096 bins is DQ_E_UNSUPPORTED.  dq_bins_destroy frees the handle (NULL: nothing); it waits
+ * for the device's outstanding work, so a dq_bin_count still running has finished with the edges.
+ * dq_bin_count: counts: int64[n_edges + 2] on the device, 8-byte aligned, the slots [below, bin 0 .. bin k-1, above,
+ * nan].  Adds to counts[slot] the number of rows among the n_rows (< 2^31) of col (a view of `type`: values, validity
+ * bitmap or NULL) in that slot.  The slot rule: a value is converted to binary64 as Spark's cast does (f32 widens
+ * exactly, integers round to nearest-even, a decimal is the correctly rounded quotient), then, with e the stored edges,
+ *     e[i] <= x < e[i+1]            bin i
+ *     x == e[k]                     the last bin, which is closed on the right
+ *     x < e[0], including -inf      below
+ *     x > e[k], including +inf      above
+ *     NaN                           nan
+ * -0.0 compares as 0.0.  NULL rows are in no slot.  The bin of a value is defined only by comparisons against the
+ * stored edges, never by a division.
+ * The call ACCUMULATES, as dq_dict_count does: the caller zeroes counts once and the chunks of a column add into one
+ * array; nothing outside counts[0, n_edges + 2) is written.  Asynchronous on hip_stream.  n_rows == 0: DQ_OK, no
+ * launch.  type: DQ_TYPE_F64 / F32 / I64 / I32 / I16 / I8 or DQ_DECIMAL128(p, s) of any precision; BOOL, DATE32,
+ * TIMESTAMP, the string types and DICT_UTF8 are DQ_E_UNSUPPORTED with the type named, before any launch.  A device
+ * other than the handle's, a NULL or misaligned buffer, reserved != 0: DQ_E_INVALID.  dq_freq_build_weighted over a
+ * string column of the k + 3 slot labels with these counts as weights is the frequency table Spark's groupBy over a
+ * binning UDF returning those labels builds. */
+typedef struct dq_bins dq_bins;
+dq_status dq_bins_create(const double* edges, int32_t n_edges, int32_t device, dq_bins** out);
+void dq_bins_destroy(dq_bins* bins);
+dq_status dq_bin_count(const dq_bins* bins, int32_t type, const dq_column_view* col, int64_t n_rows, int64_t* counts,
+                       int32_t device, void* hip_stream);
+
 /* Host: widen n indices of index_type (DQ_TYPE_I8 / I16 / I32, or the unsigned widths as -DQ_TYPE_I8 / -DQ_TYPE_I16)
  * to int32 in out (may be NULL: check only) and check 0 <= index < n_entries for every row whose validity bit
  * (LSB-first bitmap starting at bit validity_bit of validity[0]; NULL: every row) is set.  DQ_E_INVALID names the
