@@ -435,6 +435,30 @@ def _load():
     L.dq_dict_check_indices.argtypes = [c.c_int32, c.c_void_p, c.c_int64, c.c_void_p, c.c_int32, c.c_int64, c.c_void_p]
     L.dq_arrow_import_dictionary.restype = c.c_int32
     L.dq_arrow_import_dictionary.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    # row selections (`where`) of the grouping, histogram and quantile entry points: the unfiltered signatures with one
+    # selection bitmap per chunk (an array of device pointers) or per call
+    L.dq_freq_build_where.restype = c.c_int32
+    L.dq_freq_build_where.argtypes = [P(c.c_int32), c.c_int32, P(ColumnView), P(c.c_int64), P(c.c_void_p), c.c_int32,
+                                      c.c_int32, c.c_void_p, P(c.c_void_p)]
+    L.dq_freq_unique_rows_where.restype = c.c_int32
+    L.dq_freq_unique_rows_where.argtypes = [c.c_void_p, P(c.c_int32), P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p,
+                                            c.c_void_p, c.c_void_p, P(c.c_int64), P(c.c_int64)]
+    L.dq_dict_count_where.restype = c.c_int32
+    L.dq_dict_count_where.argtypes = [P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
+    L.dq_bin_count_where.restype = c.c_int32
+    L.dq_bin_count_where.argtypes = [c.c_void_p, c.c_int32, P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
+                                     c.c_int32, c.c_void_p]
+    L.dq_approx_quantiles_where.restype = c.c_int32
+    L.dq_approx_quantiles_where.argtypes = [c.c_int32, P(ColumnView), P(c.c_int64), P(c.c_void_p), c.c_int32,
+                                            P(c.c_double), c.c_int32, c.c_double, c.c_int32, c.c_void_p, P(c.c_double),
+                                            P(c.c_int64)]
+    L.dq_quantile_digest_where.restype = c.c_int32
+    L.dq_quantile_digest_where.argtypes = [c.c_int32, P(ColumnView), P(c.c_int64), P(c.c_void_p), c.c_int32, c.c_double,
+                                           c.c_int32, c.c_void_p, P(c.c_double), P(c.c_int64), c.c_int64, P(c.c_int64),
+                                           P(c.c_int64)]
+    L.dq_mutual_information_where.restype = c.c_int32
+    L.dq_mutual_information_where.argtypes = [P(c.c_int32), P(ColumnView), P(c.c_int64), P(c.c_void_p), c.c_int32,
+                                              c.c_int64, c.c_int32, c.c_void_p, P(c.c_double), P(c.c_int32)]
     if L.dq_abi_version() != ABI_VERSION:
         raise ImportError(f"libdqscan ABI {L.dq_abi_version()} != {ABI_VERSION}")
     return L
@@ -472,6 +496,8 @@ EXPORTED = [
     "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
     "dq_row_max_outputs", "dq_row_program_create", "dq_row_program_info", "dq_row_program_destroy", "dq_row_outcomes",
     "dq_freq_unique_rows", "dq_freq_contains_rows",
+    "dq_freq_build_where", "dq_freq_unique_rows_where", "dq_dict_count_where", "dq_bin_count_where",
+    "dq_approx_quantiles_where", "dq_quantile_digest_where", "dq_mutual_information_where",
     "dq_pred_pool_num_exprs", "dq_pred_pool_expr", "dq_expr_eval", "dq_expr_eval_host",
 ]
 

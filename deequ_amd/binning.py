@@ -142,9 +142,10 @@ class _DeviceBins:
         self.close()
 
 
-def bin_counts(chunks, column: str, bins: Bins):
+def bin_counts(chunks, column: str, bins: Bins, selection=None):
     """The int64[k + 3] device tensor of slot counts of `column` over the chunks: one dq_bin_count per chunk into one
-    array."""
+    array.  selection (a grouping.Selection): only its rows are counted (dq_bin_count_where), and the result is
+    (counts, the number of selected rows as the kernel counted them)."""
     import torch
 
     from .grouping import _gpu_type
@@ -152,20 +153,27 @@ def bin_counts(chunks, column: str, bins: Bins):
     dev = torch.cuda.current_device()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     counts = torch.zeros(bins.num_bins + 3, dtype=torch.int64, device=f"cuda:{dev}")
+    n_selected = None if selection is None else torch.zeros(1, dtype=torch.int64, device=f"cuda:{dev}")
     with _DeviceBins(bins, dev) as d:
-        for t in chunks:
+        for k, t in enumerate(chunks):
             col = t.columns[column]
             view = col.view()
-            L.check(L.lib.dq_bin_count(d.handle, _gpu_type(col.dtype), ctypes.byref(view), t.num_rows,
-                                       counts.data_ptr(), dev, stream))
-    return counts
+            if selection is None:
+                L.check(L.lib.dq_bin_count(d.handle, _gpu_type(col.dtype), ctypes.byref(view), t.num_rows,
+                                           counts.data_ptr(), dev, stream))
+            else:
+                L.check(L.lib.dq_bin_count_where(d.handle, _gpu_type(col.dtype), ctypes.byref(view), t.num_rows,
+                                                 selection.bitmaps[k].data_ptr(), counts.data_ptr(),
+                                                 n_selected.data_ptr(), dev, stream))
+    return counts if selection is None else (counts, int(n_selected.item()))
 
 
-def binned_frequencies(chunks, column: str, bins: Bins):
+def binned_frequencies(chunks, column: str, bins: Bins, selection=None):
     """The FrequenciesAndNumRows of `column` binned by `bins`: the slot counts (bin_counts) as the weights of a small
     utf8 table of the k + 3 slot labels (dq_freq_build_weighted).  A slot no row fell into makes no group, slots of
     equal labels make one; numRows counts every row, so the NULLs are numRows minus the table's values.  The state's
-    representative rows point into the label table, which is its source."""
+    representative rows point into the label table, which is its source.  selection: the rows that are the data;
+    numRows is their number."""
     import torch
 
     from .grouping import FreqTable, FrequenciesAndNumRows, _views
@@ -173,7 +181,10 @@ def binned_frequencies(chunks, column: str, bins: Bins):
 
     dev = torch.cuda.current_device()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    counts = bin_counts(chunks, column, bins)
+    if selection is None:
+        counts, num_rows = bin_counts(chunks, column, bins), sum(t.num_rows for t in chunks)
+    else:
+        counts, num_rows = bin_counts(chunks, column, bins, selection)
     labels = [s.encode("utf-8") for s in bins.slot_labels()]
     entries = [Table([utf8_column(column, labels, device=f"cuda:{dev}", nullable=False)])]
     types = (ctypes.c_int32 * 1)(L.TYPE_UTF8)
@@ -181,8 +192,7 @@ def binned_frequencies(chunks, column: str, bins: Bins):
     weights = (ctypes.c_void_p * 1)(counts.data_ptr())
     h = ctypes.c_void_p()
     L.check(L.lib.dq_freq_build_weighted(types, 1, views, rows, weights, 1, dev, stream, ctypes.byref(h)))
-    return FrequenciesAndNumRows(FreqTable(h, [L.TYPE_UTF8]), sum(t.num_rows for t in chunks),
-                                 source=(entries, [column]))
+    return FrequenciesAndNumRows(FreqTable(h, [L.TYPE_UTF8]), num_rows, source=(entries, [column]))
 
 
 def bins_to_json(bins: Bins) -> dict:

@@ -294,49 +294,52 @@ class Check:  # Check.scala:59-902
         return self._filterable(lambda w: _named(ReferentialIntegrity(columns, reference, w), assertion,
                                                  "ReferentialIntegrityConstraint", None, hint))
 
-    # ---- constraints on the grouping analyzers and DataType (plain addConstraint: no .where) --------
+    # ---- constraints on the grouping, histogram and quantile analyzers: filterable, the `where` is the analyzer's ----
     def isUnique(self, column, hint=None):  # Check.scala:139-141
-        return self.addConstraint(_named(Uniqueness([column]), _is_one, "UniquenessConstraint", None, hint))
+        return self._filterable(lambda w: _named(Uniqueness([column], w), _is_one, "UniquenessConstraint", None, hint))
 
     def isPrimaryKey(self, column, *columns):  # Check.scala:151-153
-        return self.addConstraint(_named(Uniqueness([column, *columns]), _is_one, "UniquenessConstraint"))
+        return self._filterable(lambda w: _named(Uniqueness([column, *columns], w), _is_one, "UniquenessConstraint"))
 
     def hasUniqueness(self, columns, assertion, hint=None):  # Check.scala:176-221
-        return self.addConstraint(_named(Uniqueness(columns), assertion, "UniquenessConstraint", None, hint))
+        return self._filterable(lambda w: _named(Uniqueness(columns, w), assertion, "UniquenessConstraint", None, hint))
 
     def hasDistinctness(self, columns, assertion, hint=None):  # Check.scala:232-238
-        return self.addConstraint(_named(Distinctness(columns), assertion, "DistinctnessConstraint", None, hint))
+        return self._filterable(lambda w: _named(Distinctness(columns, w), assertion, "DistinctnessConstraint", None,
+                                                 hint))
 
     def hasUniqueValueRatio(self, columns, assertion, hint=None):  # Check.scala:249-256
-        a = UniqueValueRatio(columns)
-        # (Constraint.scala:254 leaves the name's parenthesis open)
-        return self.addConstraint(NamedConstraint(AnalysisBasedConstraint(a, assertion, None, hint),
-                                                  f"UniqueValueRatioConstraint({a}"))
+        def create(w):
+            a = UniqueValueRatio(columns, w)
+            # (Constraint.scala:254 leaves the name's parenthesis open)
+            return NamedConstraint(AnalysisBasedConstraint(a, assertion, None, hint), f"UniqueValueRatioConstraint({a}")
+        return self._filterable(create)
 
     def hasNumberOfDistinctValues(self, column, assertion, binningUdf=None, maxBins=Histogram.MaximumAllowedDetailBins,
                                   hint=None, *, binning=None):
         # Check.scala:269-278, histogramBinConstraint (Constraint.scala:133-147); binning: a binning.Bins
-        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins, binning), assertion,
-                                         "HistogramBinConstraint", lambda d: d.numberOfBins, hint))
+        return self._filterable(lambda w: _named(Histogram(column, binningUdf, maxBins, binning, where=w), assertion,
+                                                 "HistogramBinConstraint", lambda d: d.numberOfBins, hint))
 
     def hasHistogramValues(self, column, assertion, binningUdf=None, maxBins=Histogram.MaximumAllowedDetailBins,
                            hint=None, *, binning=None):  # Check.scala:295-304; binning: a binning.Bins
-        return self.addConstraint(_named(Histogram(column, binningUdf, maxBins, binning), assertion,
-                                         "HistogramConstraint", None, hint))
+        return self._filterable(lambda w: _named(Histogram(column, binningUdf, maxBins, binning, where=w), assertion,
+                                                 "HistogramConstraint", None, hint))
 
     def hasEntropy(self, column, assertion, hint=None):  # Check.scala:353-360
-        return self.addConstraint(_named(Entropy(column), assertion, "EntropyConstraint", None, hint))
+        return self._filterable(lambda w: _named(Entropy(column, w), assertion, "EntropyConstraint", None, hint))
 
     def hasMutualInformation(self, columnA, columnB, assertion, hint=None):  # Check.scala:371-379
-        return self.addConstraint(_named(MutualInformation(columnA, columnB), assertion, "MutualInformationConstraint",
-                                         None, hint))
+        return self._filterable(lambda w: _named(MutualInformation(columnA, columnB, w), assertion,
+                                                 "MutualInformationConstraint", None, hint))
 
+    # ---- DataType (plain addConstraint: no .where) -------------------------------------------------
     def hasDataType(self, column, dataType, assertion=_is_one, hint=None):  # Check.scala:653-661
         return self.addConstraint(data_type_constraint(column, dataType, assertion, hint))
 
     def hasApproxQuantile(self, column, quantile, assertion, hint=None):  # Check.scala:391-398
-        return self.addConstraint(_named(ApproxQuantile(column, quantile), assertion, "ApproxQuantileConstraint",
-                                         None, hint))
+        return self._filterable(lambda w: _named(ApproxQuantile(column, quantile, where=w), assertion,
+                                                 "ApproxQuantileConstraint", None, hint))
 
     # the pattern checks of Check.scala:581-642; a pattern outside the GPU regex subset (the credit card and social
     # security number patterns) gives the failure metric PatternMatch gives for it

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdint>
 #include <new>
+#include <type_traits>
 
 #include "dq_decimal.h"
 #include "dq_device.h"
@@ -97,8 +98,12 @@ __device__ __forceinline__ uint32_t bin_slot(double x, const double* e, int32_t 
 // with one 64-bit global add, at the end.  Before the LDS add the lanes that share the slot of the group's first
 // selected row are combined into one add of their number: a column that falls into one bin costs one LDS add per
 // group, not 64 adds to one address; the other lanes add 1 each.
-template <int TYPE>
+// SEL: `mask` is the selection bitmap -- a group's word is validity & mask -- and the selected rows (NULL ones too)
+// are counted per wave and added to *n_selected (when wanted) with one global add per wave at the end.
+template <int TYPE, bool SEL>
 __global__ __launch_bounds__(kBlock) void dq_bin_count_kernel(const void* __restrict__ values, const uint32_t* validity,
+                                                              const uint32_t* mask,
+                                                              unsigned long long* __restrict__ n_selected,
                                                               const double* __restrict__ gedges, int32_t k,
                                                               int32_t guess, double inv, int32_t scale, int32_t narrow,
                                                               int64_t n_rows, int64_t rows_per_range,
@@ -115,13 +120,22 @@ __global__ __launch_bounds__(kBlock) void dq_bin_count_kernel(const void* __rest
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int32_t nr = (int32_t)(row1 - row0);
+  uint32_t nsel = 0;  // SEL: this wave's selected rows (wave-uniform; a range is below 2^31 rows)
   for (int32_t rb = wave * 512; rb < nr; rb += kRowsPerIter) {
 #pragma unroll 2
     for (int j = 0; j < 8; ++j) {
       const int32_t left = nr - rb - 64 * j;  // rows of this group below row1
       if (left <= 0) break;
       const int64_t gbase = row0 + rb + 64 * j;
-      const uint64_t m = sel_word(validity, gbase >> 5, left);
+      uint64_t m;
+      if constexpr (SEL) {
+        const uint64_t s = sel_word(mask, gbase >> 5, left);
+        nsel += (uint32_t)__builtin_popcountll(s);
+        if (s == 0) continue;
+        m = s & sel_word(validity, gbase >> 5, left);
+      } else {
+        m = sel_word(validity, gbase >> 5, left);
+      }
       if (m == 0) continue;
       const bool sel = lane_bit(m);
       uint32_t slot = 0;
@@ -138,6 +152,13 @@ __global__ __launch_bounds__(kBlock) void dq_bin_count_kernel(const void* __rest
     const uint32_t c = cnt[s];
     if (c) atomicAdd(&counts[s], (unsigned long long)c);
   }
+  if constexpr (SEL) {
+    if (n_selected && lane == 0 && nsel) atomicAdd(n_selected, (unsigned long long)nsel);
+  }
+}
+
+__global__ void bin_add_rows(unsigned long long* __restrict__ n_selected, unsigned long long n) {
+  atomicAdd(n_selected, n);
 }
 
 const char* bin_type_name(int32_t type) {
@@ -201,10 +222,12 @@ dq_status dq_bins_create(const double* edges, int32_t n_edges, int32_t device, d
 
 void dq_bins_destroy(dq_bins* bins) { delete bins; }
 
-dq_status dq_bin_count(const dq_bins* bins, int32_t type, const dq_column_view* col, int64_t n_rows, int64_t* counts,
-                       int32_t device, void* hip_stream) {
+static dq_status bin_count_impl(const char* me, const dq_bins* bins, int32_t type, const dq_column_view* col,
+                                int64_t n_rows, const uint64_t* selection, int64_t* counts, int64_t* n_selected,
+                                int32_t device, void* hip_stream) {
   using namespace dq;
-  const char* me = "dq_bin_count";
+  if (((uintptr_t)selection & 7) || ((uintptr_t)n_selected & 7))
+    return set_error(DQ_E_INVALID, "%s: the selection / n_selected is not 8-byte aligned", me);
   if (!bins) return set_error(DQ_E_INVALID, "%s: bad argument", me);
   const int32_t base = type_valid(type) || type == DQ_TYPE_DICT_UTF8 ? DQ_TYPE_BASE(type) : 0;
   int32_t width = 0;
@@ -236,20 +259,44 @@ dq_status dq_bin_count(const dq_bins* bins, int32_t type, const dq_column_view* 
   const int32_t narrow = base == DQ_TYPE_DECIMAL128 && DQ_DECIMAL_PRECISION(type) <= 18;
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), bin_lds_bytes(k), st, col->values,
-                       reinterpret_cast<const uint32_t*>(col->validity), bins->edges.get(), k, bins->guess, bins->inv,
+                       reinterpret_cast<const uint32_t*>(col->validity), reinterpret_cast<const uint32_t*>(selection),
+                       reinterpret_cast<unsigned long long*>(n_selected), bins->edges.get(), k, bins->guess, bins->inv,
                        scale, narrow, n_rows, rows_per_range, reinterpret_cast<unsigned long long*>(counts));
   };
-  switch (base) {
-    case DQ_TYPE_F64: launch(dq_bin_count_kernel<DQ_TYPE_F64>); break;
-    case DQ_TYPE_F32: launch(dq_bin_count_kernel<DQ_TYPE_F32>); break;
-    case DQ_TYPE_I64: launch(dq_bin_count_kernel<DQ_TYPE_I64>); break;
-    case DQ_TYPE_I32: launch(dq_bin_count_kernel<DQ_TYPE_I32>); break;
-    case DQ_TYPE_I16: launch(dq_bin_count_kernel<DQ_TYPE_I16>); break;
-    case DQ_TYPE_I8: launch(dq_bin_count_kernel<DQ_TYPE_I8>); break;
-    default: launch(dq_bin_count_kernel<DQ_TYPE_DECIMAL128>); break;
+  auto launch_type = [&](auto filtered) {
+    constexpr bool F = decltype(filtered)::value;
+    switch (base) {
+      case DQ_TYPE_F64: launch(dq_bin_count_kernel<DQ_TYPE_F64, F>); break;
+      case DQ_TYPE_F32: launch(dq_bin_count_kernel<DQ_TYPE_F32, F>); break;
+      case DQ_TYPE_I64: launch(dq_bin_count_kernel<DQ_TYPE_I64, F>); break;
+      case DQ_TYPE_I32: launch(dq_bin_count_kernel<DQ_TYPE_I32, F>); break;
+      case DQ_TYPE_I16: launch(dq_bin_count_kernel<DQ_TYPE_I16, F>); break;
+      case DQ_TYPE_I8: launch(dq_bin_count_kernel<DQ_TYPE_I8, F>); break;
+      default: launch(dq_bin_count_kernel<DQ_TYPE_DECIMAL128, F>); break;
+    }
+  };
+  if (selection) {
+    launch_type(std::true_type{});
+  } else {
+    launch_type(std::false_type{});
+    if (n_selected) {  // every row is selected
+      hipLaunchKernelGGL(bin_add_rows, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long*>(n_selected),
+                         (unsigned long long)n_rows);
+    }
   }
   DQ_HIP(hipGetLastError());
   return DQ_OK;
+}
+
+dq_status dq_bin_count(const dq_bins* bins, int32_t type, const dq_column_view* col, int64_t n_rows, int64_t* counts,
+                       int32_t device, void* hip_stream) {
+  return bin_count_impl("dq_bin_count", bins, type, col, n_rows, nullptr, counts, nullptr, device, hip_stream);
+}
+
+dq_status dq_bin_count_where(const dq_bins* bins, int32_t type, const dq_column_view* col, int64_t n_rows,
+                             const uint64_t* selection, int64_t* counts, int64_t* n_selected, int32_t device,
+                             void* hip_stream) {
+  return bin_count_impl("dq_bin_count_where", bins, type, col, n_rows, selection, counts, n_selected, device, hip_stream);
 }
 
 }  // extern "C"

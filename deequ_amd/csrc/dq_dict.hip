@@ -245,9 +245,11 @@ constexpr int32_t kDictCountMaxWG = 2048;  // row ranges per launch: eight workg
 // workgroup, entry e by lane e % 256 (consecutive 8-byte adds), where the entry's non-NULL bit is looked at -- once
 // per entry and workgroup, not per row.  Not STAGED: one global add per counted row.  (Combining the equal indices
 // of a 64-row group before the LDS add -- one pass per distinct index -- was measured and lost)
-template <bool STAGED>
+// SEL: the group's word is validity & mask, mask being the selection bitmap (dq_lane.h's sel_word: one more scalar
+// load per 64 rows).
+template <bool STAGED, bool SEL>
 __global__ __launch_bounds__(kBlock) void dq_dict_count_kernel(const int32_t* __restrict__ indices,
-                                                               const uint32_t* validity,
+                                                               const uint32_t* validity, const uint32_t* mask,
                                                                const uint32_t* __restrict__ gtab, uint32_t D,
                                                                int64_t n_rows, int64_t rows_per_range,
                                                                unsigned long long* __restrict__ counts) {
@@ -268,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void dq_dict_count_kernel(const int32_t* __
       const int32_t left = nr - rb - 64 * j;  // rows of this group below row1
       if (left <= 0) break;
       const int64_t gbase = row0 + rb + 64 * j;
-      const uint64_t m = sel_word(validity, gbase >> 5, left);
+      const uint64_t m = SEL ? sel_word(validity, mask, gbase >> 5, left) : sel_word(validity, gbase >> 5, left);
       if (m == 0) continue;
       uint32_t idx = D;
       if (lane_bit(m)) idx = (uint32_t)indices[gbase + lane];
@@ -353,10 +355,10 @@ dq_status dq_dict_decode(int32_t dict_type, const dq_column_view* dict, int64_t 
                       values_capacity, out_offsets, data_bytes, st, me);
 }
 
-dq_status dq_dict_count(const dq_column_view* indices, int64_t n_rows, int64_t* counts, int32_t device,
-                        void* hip_stream) {
+static dq_status dict_count_impl(const char* me, const dq_column_view* indices, int64_t n_rows,
+                                 const uint64_t* selection, int64_t* counts, int32_t device, void* hip_stream) {
   using namespace dq;
-  const char* me = "dq_dict_count";
+  if ((uintptr_t)selection & 7) return set_error(DQ_E_INVALID, "%s: the selection is not 8-byte aligned", me);
   if (!indices || indices->reserved < 0 || indices->reserved > INT32_MAX || n_rows < 0)
     return set_error(DQ_E_INVALID, "%s: bad argument", me);
   if (n_rows > INT32_MAX) return set_error(DQ_E_UNSUPPORTED, "%s: at most 2^31 - 1 rows per call", me);
@@ -378,14 +380,29 @@ dq_status dq_dict_count(const dq_column_view* indices, int64_t n_rows, int64_t* 
   const bool staged = D <= (uint32_t)kDictCountLdsEntries && !(knob && std::strcmp(knob, "global") == 0);
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, static_cast<const int32_t*>(indices->values),
-                       reinterpret_cast<const uint32_t*>(indices->validity),
+                       reinterpret_cast<const uint32_t*>(indices->validity), reinterpret_cast<const uint32_t*>(selection),
                        static_cast<const uint32_t*>(indices->offsets), D, n_rows, rows_per_range,
                        reinterpret_cast<unsigned long long*>(counts));
   };
-  if (staged) launch(dq_dict_count_kernel<true>);
-  else launch(dq_dict_count_kernel<false>);
+  if (selection) {
+    if (staged) launch(dq_dict_count_kernel<true, true>);
+    else launch(dq_dict_count_kernel<false, true>);
+  } else {
+    if (staged) launch(dq_dict_count_kernel<true, false>);
+    else launch(dq_dict_count_kernel<false, false>);
+  }
   DQ_HIP(hipGetLastError());
   return DQ_OK;
+}
+
+dq_status dq_dict_count(const dq_column_view* indices, int64_t n_rows, int64_t* counts, int32_t device,
+                        void* hip_stream) {
+  return dict_count_impl("dq_dict_count", indices, n_rows, nullptr, counts, device, hip_stream);
+}
+
+dq_status dq_dict_count_where(const dq_column_view* indices, int64_t n_rows, const uint64_t* selection, int64_t* counts,
+                              int32_t device, void* hip_stream) {
+  return dict_count_impl("dq_dict_count_where", indices, n_rows, selection, counts, device, hip_stream);
 }
 
 }  // extern "C"

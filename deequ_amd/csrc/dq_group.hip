@@ -145,10 +145,14 @@ constexpr int kCompactRows = 256 * kCompactPer;
 // which the keys differ: the radix sort skips the common high bits)
 // HASHED: keys are tuple hashes (any columns); else one numeric column whose value bits are the keys -- its next
 // tile's values and validity words are loaded before this tile's work (in flight behind it)
-template <bool HASHED>
+// SEL: only the rows whose bit is set in `sel` take part -- the chunk's selection bitmap, read as the 32-bit words the
+// validity is read as (a little-endian uint64_t word is its two uint32_t halves in row order), so the unhashed path
+// ANDs it into the prefetched validity word and the hashed path tests it before the row is hashed
+template <bool HASHED, bool SEL>
 __global__ __launch_bounds__(256) void group_compact(GroupCols g, int64_t n, int64_t chunk,
                                                      uint64_t* __restrict__ out_keys, uint64_t* __restrict__ out_rows,
-                                                     unsigned long long* __restrict__ cursor) {
+                                                     unsigned long long* __restrict__ cursor,
+                                                     const uint32_t* __restrict__ sel) {
   __shared__ uint32_t wave_n[4];
   __shared__ unsigned long long tile_base;
   __shared__ unsigned long long wave_and[4], wave_or[4];
@@ -168,6 +172,7 @@ __global__ __launch_bounds__(256) void group_compact(GroupCols g, int64_t n, int
         if (r < n) {
           nval[u] = value_bits(g, 0, r);
           nvw[u] = g.validity[0] ? g.validity[0][r >> 5] : 0xFFFFFFFFu;
+          if constexpr (SEL) nvw[u] &= sel[r >> 5];
         }
       }
     }
@@ -192,7 +197,8 @@ __global__ __launch_bounds__(256) void group_compact(GroupCols g, int64_t n, int
       const int64_t r = t0 + u * 256 + threadIdx.x;
       bool v;
       if constexpr (HASHED) {
-        v = r < n && row_valid(g, r);
+        if constexpr (SEL) v = r < n && ((sel[r >> 5] >> (r & 31)) & 1u) && row_valid(g, r);
+        else v = r < n && row_valid(g, r);
         key[u] = v ? tuple_key(g, r) : 0;
       } else {
         v = r < n && ((cvw[u] >> (r & 31)) & 1u);
@@ -841,17 +847,21 @@ __global__ void find_groups(const uint64_t* __restrict__ want, int32_t n, const 
 // words, written by lane 0 (rows past n vote 0, so the last word's tail is 0).  The build has checked that equal keys
 // are equal tuples, so a found key is the row's group; a key the table lacks raises *missing.  tot[0] / tot[1]: the
 // set bits of the two bitmaps.
-template <bool HASHED>
+// SEL: a row outside the selection bitmap `sel` (one word per wave and step: word w) is in neither bitmap.
+template <bool HASHED, bool SEL>
 __global__ __launch_bounds__(256) void unique_rows(GroupCols g, int64_t n, const uint64_t* __restrict__ keys,
                                                    const int64_t* __restrict__ counts, int64_t G,
                                                    uint64_t* __restrict__ unique, uint64_t* __restrict__ grouped,
-                                                   unsigned long long* __restrict__ tot, int32_t* __restrict__ missing) {
+                                                   unsigned long long* __restrict__ tot, int32_t* __restrict__ missing,
+                                                   const uint64_t* __restrict__ sel) {
   const int lane = threadIdx.x & 63;
   const int64_t words = (n + 63) >> 6;
   unsigned long long nu = 0, ng = 0;
   for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < words; w += (int64_t)gridDim.x * 4) {
     const int64_t r = w * 64 + lane;
-    const bool v = r < n && row_valid(g, r);
+    bool v = r < n;
+    if constexpr (SEL) v = v && ((sel[w] >> lane) & 1ull);
+    v = v && row_valid(g, r);
     bool one = false;
     if (v) {
       const uint64_t k = HASHED ? tuple_key(g, r) : value_bits(g, 0, r);
@@ -1151,7 +1161,8 @@ static dq_status mi_from_joint(Frame& fr, dq_freq_table* t, const uint64_t* sort
 
 static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_column_view* cols,
                                  const int64_t* chunk_rows, int32_t n_chunks, int32_t device, void* hip_stream,
-                                 dq_freq_table** out, const MiRequest* mi, const int64_t* const* weights = nullptr) {
+                                 dq_freq_table** out, const MiRequest* mi, const int64_t* const* weights = nullptr,
+                                 const uint64_t* const* selection = nullptr) {
   if (!out) return set_error(DQ_E_INVALID, "dq_freq_build: out is NULL");
   *out = nullptr;
   if (n_cols < 1 || n_cols > kMaxGroupCols || !types)
@@ -1161,6 +1172,9 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
   for (int k = 0; weights && k < n_chunks; ++k)
     if (chunk_rows[k] > 0 && (!weights[k] || ((uintptr_t)weights[k] & 7)))
       return set_error(DQ_E_INVALID, "dq_freq_build_weighted: chunk %d has no (or misaligned) weights", k);
+  for (int k = 0; selection && k < n_chunks; ++k)
+    if ((uintptr_t)selection[k] & 7)
+      return set_error(DQ_E_INVALID, "dq_freq_build_where: chunk %d's selection is not 8-byte aligned", k);
   for (int c = 0; c < n_cols; ++c) {
     if (!type_valid(types[c]))
       return set_error(DQ_E_TYPE, "dq_freq_build: column %d has unknown type %d", c, types[c]);
@@ -1207,9 +1221,13 @@ static dq_status freq_build_impl(const int32_t* types, int32_t n_cols, const dq_
     const int64_t n = chunk_rows[k];
     if (n == 0) continue;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + kCompactRows - 1) / kCompactRows));
+    // (a chunk without a selection runs the unfiltered instantiation)
+    const uint32_t* const sel = selection ? reinterpret_cast<const uint32_t*>(selection[k]) : nullptr;
     with_bool(t->hashed != 0, [&](auto hashed) {  // (sel_rows is NULL for an exact-key table)
-      hipLaunchKernelGGL(group_compact<decltype(hashed)::value>, dim3(grid), dim3(256), 0, S, gcs[k], n, (int64_t)k,
-                         sel_keys, sel_rows, nsel);
+      with_bool(sel != nullptr, [&](auto filtered) {
+        hipLaunchKernelGGL((group_compact<decltype(hashed)::value, decltype(filtered)::value>), dim3(grid), dim3(256), 0, S,
+                           gcs[k], n, (int64_t)k, sel_keys, sel_rows, nsel, sel);
+      });
     });
     DQ_HIP(hipGetLastError());
   }
@@ -1361,6 +1379,12 @@ dq_status dq_freq_build(const int32_t* types, int32_t n_cols, const dq_column_vi
   return freq_build_impl(types, n_cols, cols, chunk_rows, n_chunks, device, hip_stream, out, nullptr);
 }
 
+dq_status dq_freq_build_where(const int32_t* types, int32_t n_cols, const dq_column_view* cols, const int64_t* chunk_rows,
+                              const uint64_t* const* selection, int32_t n_chunks, int32_t device, void* hip_stream,
+                              dq_freq_table** out) {
+  return freq_build_impl(types, n_cols, cols, chunk_rows, n_chunks, device, hip_stream, out, nullptr, nullptr, selection);
+}
+
 dq_status dq_freq_build_weighted(const int32_t* types, int32_t n_cols, const dq_column_view* cols,
                                  const int64_t* chunk_rows, const int64_t* const* weights, int32_t n_chunks,
                                  int32_t device, void* hip_stream, dq_freq_table** out) {
@@ -1375,6 +1399,17 @@ dq_status dq_mutual_information(const int32_t* types, const dq_column_view* cols
   MiRequest mi{(double)num_rows, value, defined};
   dq_freq_table* unused = nullptr;
   dq_status s = freq_build_impl(types, 2, cols, chunk_rows, n_chunks, device, hip_stream, &unused, &mi);
+  if (unused) dq_freq_destroy(unused);
+  return s;
+}
+
+dq_status dq_mutual_information_where(const int32_t* types, const dq_column_view* cols, const int64_t* chunk_rows,
+                                      const uint64_t* const* selection, int32_t n_chunks, int64_t num_rows,
+                                      int32_t device, void* hip_stream, double* value, int32_t* defined) {
+  if (!value || !defined) return set_error(DQ_E_INVALID, "dq_mutual_information_where: NULL output");
+  MiRequest mi{(double)num_rows, value, defined};
+  dq_freq_table* unused = nullptr;
+  dq_status s = freq_build_impl(types, 2, cols, chunk_rows, n_chunks, device, hip_stream, &unused, &mi, nullptr, selection);
   if (unused) dq_freq_destroy(unused);
   return s;
 }
@@ -1796,9 +1831,9 @@ dq_status dq_freq_take_values(const dq_freq_table* t, const uint64_t* keys, int3
   return DQ_OK;
 }
 
-dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols, int64_t n_rows,
-                              uint64_t* unique, uint64_t* grouped, void* hip_stream, int64_t* num_unique,
-                              int64_t* num_grouped) {
+static dq_status unique_rows_impl(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols,
+                                  int64_t n_rows, const uint64_t* selection, uint64_t* unique, uint64_t* grouped,
+                                  void* hip_stream, int64_t* num_unique, int64_t* num_grouped) {
   if (!t) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: table is NULL");
   if (n_rows < 0 || n_rows >= (1ll << 31)) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: 0 <= n_rows < 2^31");
   if (n_rows == 0) {
@@ -1808,7 +1843,7 @@ dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, cons
   }
   const int n_cols = (int)t->types.size();
   if (!cols) return set_error(DQ_E_INVALID, "dq_freq_unique_rows: cols is NULL");
-  if (!unique || ((uintptr_t)unique & 7) || ((uintptr_t)grouped & 7))
+  if (!unique || ((uintptr_t)unique & 7) || ((uintptr_t)grouped & 7) || ((uintptr_t)selection & 7))
     return set_error(DQ_E_INVALID, "dq_freq_unique_rows: the bitmaps must be 8-byte aligned device buffers");
   auto is_str = [](int32_t ty) { return ty == DQ_TYPE_UTF8 || ty == DQ_TYPE_LARGE_UTF8; };
   std::vector<int32_t> ty(t->types);
@@ -1831,8 +1866,11 @@ dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, cons
   const int64_t words = (n_rows + 63) / 64;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(8192, (words + 3) / 4));
   with_bool(t->hashed != 0, [&](auto hashed) {
-    hipLaunchKernelGGL(unique_rows<decltype(hashed)::value>, dim3(grid), dim3(256), 0, S, g, n_rows, t->d_keys.get(),
-                       t->d_counts.get(), t->n_groups, unique, grouped, d_out, reinterpret_cast<int32_t*>(d_out + 2));
+    with_bool(selection != nullptr, [&](auto filtered) {
+      hipLaunchKernelGGL((unique_rows<decltype(hashed)::value, decltype(filtered)::value>), dim3(grid), dim3(256), 0, S, g,
+                         n_rows, t->d_keys.get(), t->d_counts.get(), t->n_groups, unique, grouped, d_out,
+                         reinterpret_cast<int32_t*>(d_out + 2), selection);
+    });
   });
   DQ_HIP(hipGetLastError());
   unsigned long long h[4];
@@ -1842,6 +1880,18 @@ dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, cons
   if (num_unique) *num_unique = (int64_t)h[0];
   if (num_grouped) *num_grouped = (int64_t)h[1];
   return DQ_OK;
+}
+
+dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols, int64_t n_rows,
+                              uint64_t* unique, uint64_t* grouped, void* hip_stream, int64_t* num_unique,
+                              int64_t* num_grouped) {
+  return unique_rows_impl(t, types, cols, n_rows, nullptr, unique, grouped, hip_stream, num_unique, num_grouped);
+}
+
+dq_status dq_freq_unique_rows_where(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols,
+                                    int64_t n_rows, const uint64_t* selection, uint64_t* unique, uint64_t* grouped,
+                                    void* hip_stream, int64_t* num_unique, int64_t* num_grouped) {
+  return unique_rows_impl(t, types, cols, n_rows, selection, unique, grouped, hip_stream, num_unique, num_grouped);
 }
 
 dq_status dq_freq_contains_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols,

@@ -90,9 +90,12 @@ __device__ __forceinline__ void q_count(uint64_t key, bool ok, int32_t shift, ui
 
 // Pass over a column chunk: each thread reads 16-byte vectors (V rows; V = 1 when the values are not
 // 16-byte aligned), kQUnroll of them in flight, grid-stride; one validity word per vector.
-template <int TYPE, int V, bool APPEND>
+// SEL: `rowsel` is the chunk's selection bitmap read as the 32-bit words the validity is read as (the two halves of a
+// little-endian 64-bit word, in row order): the vector's validity bits ANDed with its selection bits.
+template <int TYPE, int V, bool APPEND, bool SEL>
 __global__ __launch_bounds__(kQBlock) void dq_quantile_hist(const void* __restrict__ values,
-                                                            const uint32_t* __restrict__ validity, int64_t n,
+                                                            const uint32_t* __restrict__ validity,
+                                                            const uint32_t* __restrict__ rowsel, int64_t n,
                                                             int32_t shift, uint32_t dmask, int32_t nq, QSelect sel,
                                                             unsigned long long* __restrict__ hist,
                                                             unsigned long long* __restrict__ andor) {
@@ -130,11 +133,16 @@ __global__ __launch_bounds__(kQBlock) void dq_quantile_hist(const void* __restri
           raw[u][0] = __builtin_nontemporal_load(v + r);
         }
         vw[u] = validity ? (validity[r >> 5] >> (r & 31)) : 0xFFFFFFFFu;
+        if constexpr (SEL) vw[u] &= rowsel[r >> 5] >> (r & 31);
       } else {
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           raw[u][e] = r + e < n ? v[r + e] : 0;
-          if (r + e < n) vw[u] |= (validity ? (validity[(r + e) >> 5] >> ((r + e) & 31)) & 1u : 1u) << e;
+          if (r + e < n) {
+            uint32_t bit = validity ? (validity[(r + e) >> 5] >> ((r + e) & 31)) & 1u : 1u;
+            if constexpr (SEL) bit &= rowsel[(r + e) >> 5] >> ((r + e) & 31);
+            vw[u] |= bit << e;
+          }
         }
       }
     }
@@ -288,16 +296,23 @@ __global__ __launch_bounds__(kQBlock) void dq_quantile_cand_hist(const unsigned 
     if (lds_hist[i]) atomicAdd(&hist[i], (unsigned long long)lds_hist[i]);
 }
 
+template <int TYPE, int V, bool SEL>
+void launch_hist_sel(bool append, int grid, size_t lds, hipStream_t st, const void* values, const uint32_t* val,
+                     const uint32_t* rowsel, int64_t rows, int shift, uint32_t dmask, int nq, const QSelect& sel,
+                     unsigned long long* hist, unsigned long long* andor) {
+  if (append)
+    hipLaunchKernelGGL((dq_quantile_hist<TYPE, V, true, SEL>), dim3(grid), dim3(kQBlock), lds, st, values, val, rowsel,
+                       rows, shift, dmask, nq, sel, hist, nullptr);
+  else
+    hipLaunchKernelGGL((dq_quantile_hist<TYPE, V, false, SEL>), dim3(grid), dim3(kQBlock), lds, st, values, val, rowsel,
+                       rows, shift, dmask, nq, sel, hist, andor);
+}
 template <int TYPE, int V>
 void launch_hist(bool append, int grid, size_t lds, hipStream_t st, const void* values, const uint32_t* val,
-                 int64_t rows, int shift, uint32_t dmask, int nq, const QSelect& sel, unsigned long long* hist,
-                 unsigned long long* andor) {
-  if (append)
-    hipLaunchKernelGGL((dq_quantile_hist<TYPE, V, true>), dim3(grid), dim3(kQBlock), lds, st, values, val, rows, shift,
-                       dmask, nq, sel, hist, nullptr);
-  else
-    hipLaunchKernelGGL((dq_quantile_hist<TYPE, V, false>), dim3(grid), dim3(kQBlock), lds, st, values, val, rows,
-                       shift, dmask, nq, sel, hist, andor);
+                 const uint32_t* rowsel, int64_t rows, int shift, uint32_t dmask, int nq, const QSelect& sel,
+                 unsigned long long* hist, unsigned long long* andor) {
+  if (rowsel) launch_hist_sel<TYPE, V, true>(append, grid, lds, st, values, val, rowsel, rows, shift, dmask, nq, sel, hist, andor);
+  else launch_hist_sel<TYPE, V, false>(append, grid, lds, st, values, val, nullptr, rows, shift, dmask, nq, sel, hist, andor);
 }
 
 // stream-ordered scratch from a pool of this library's own per device (hipMallocFromPoolAsync): the digest's
@@ -357,9 +372,11 @@ constexpr int kDAndOrCopies = 16;            // the candidates' AND / OR: copies
 constexpr int64_t kDCandBudget = int64_t(1) << 26;  // candidates per compaction batch (~1.6 GB of scratch)
 
 // the key of row i * n / m of a chunk (i < m; ~0 for a NULL row), and whether the row is non-null
+// (an unselected row -- sel: the selection bitmap as 32-bit words, or NULL -- is dropped as a NULL row is)
 template <int TYPE>
 __global__ __launch_bounds__(kQBlock) void dq_digest_sample(const void* __restrict__ values,
-                                                            const uint32_t* __restrict__ validity, int64_t n, int64_t m,
+                                                            const uint32_t* __restrict__ validity,
+                                                            const uint32_t* __restrict__ sel, int64_t n, int64_t m,
                                                             unsigned long long* __restrict__ keys,
                                                             unsigned char* __restrict__ ok) {
   const int64_t i = (int64_t)blockIdx.x * kQBlock + threadIdx.x;
@@ -368,7 +385,8 @@ __global__ __launch_bounds__(kQBlock) void dq_digest_sample(const void* __restri
   uint64_t raw;
   if constexpr (TYPE == DQ_TYPE_I32) raw = (uint32_t)reinterpret_cast<const int32_t*>(values)[r];
   else raw = reinterpret_cast<const uint64_t*>(values)[r];
-  const bool valid = validity ? ((validity[r >> 5] >> (r & 31)) & 1u) != 0 : true;
+  const bool valid = (validity ? ((validity[r >> 5] >> (r & 31)) & 1u) != 0 : true) &&
+                     (sel ? ((sel[r >> 5] >> (r & 31)) & 1u) != 0 : true);
   keys[i] = valid ? order_key<TYPE>(raw) : ~0ull;  // a NULL sorts last (the host keeps the first #valid keys)
   ok[i] = (unsigned char)valid;
 }
@@ -434,9 +452,12 @@ __device__ __forceinline__ void digest_buckets(const unsigned long long* spl, co
 // buckets appended to cand[*cursor ...] (order free: sorted next), staged in the workgroup's LDS and flushed
 // with one global atomic per kDStage - kQBlock keys (one cursor for the whole launch: a per-wave global atomic
 // on it ran 17 ms per 1e8 rows, r4l)
-template <int TYPE, bool COUNT>
+// SEL: the prefetched validity word is ANDed with the selection's word of the same rows (sel: the selection bitmap
+// as 32-bit words).
+template <int TYPE, bool COUNT, bool SEL>
 __global__ __launch_bounds__(kQBlock) void dq_digest_pass(const void* __restrict__ values,
-                                                          const uint32_t* __restrict__ validity, int64_t n,
+                                                          const uint32_t* __restrict__ validity,
+                                                          const uint32_t* __restrict__ sel, int64_t n,
                                                           const unsigned long long* __restrict__ splitters,
                                                           const uint16_t* __restrict__ first_g, DigestCells C,
                                                           unsigned long long* __restrict__ counts,
@@ -477,6 +498,7 @@ __global__ __launch_bounds__(kQBlock) void dq_digest_pass(const void* __restrict
       vw_n[u] = 0;
       if (r < n) {
         vw_n[u] = validity ? validity[r >> 5] : 0xFFFFFFFFu;
+        if constexpr (SEL) vw_n[u] &= sel[r >> 5];
         if constexpr (TYPE == DQ_TYPE_I32) raw_n[u] = (uint32_t)__builtin_nontemporal_load(reinterpret_cast<const int32_t*>(values) + r);
         else raw_n[u] = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(values) + r);
       }
@@ -657,6 +679,12 @@ struct Widened {
   }
 };
 
+// f(std::true_type / std::false_type): whether a chunk has a selection, as a template argument
+template <typename F> void with_sel(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 bool is_narrow(int32_t type) {
   return type == DQ_TYPE_F32 || type == DQ_TYPE_I16 || type == DQ_TYPE_I8 || (type_valid(type) && is_decimal(type));
 }
@@ -738,9 +766,18 @@ using namespace dq;
 
 extern "C" {
 
-dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows, int32_t n_chunks,
-                              const double* quantiles, int32_t n_q, double relative_error, int32_t device,
-                              void* hip_stream, double* out, int64_t* count) {
+// every selection pointer 8-byte aligned (NULL entries, or no array at all: every row)
+static dq_status check_selection(const char* fn, const uint64_t* const* selection, int32_t n_chunks) {
+  for (int c = 0; selection && c < n_chunks; ++c)
+    if ((uintptr_t)selection[c] & 7)
+      return set_error(DQ_E_INVALID, "%s: chunk %d's selection is not 8-byte aligned", fn, c);
+  return DQ_OK;
+}
+
+static dq_status approx_quantiles_impl(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows,
+                                       const uint64_t* const* selection, int32_t n_chunks, const double* quantiles,
+                                       int32_t n_q, double relative_error, int32_t device, void* hip_stream,
+                                       double* out, int64_t* count) {
   if (!cols || !chunk_rows || !quantiles || !out || !count || n_chunks < 0)
     return set_error(DQ_E_INVALID, "dq_approx_quantiles: NULL argument");
   if (n_q < 1 || n_q > DQ_MAX_QUANTILES)
@@ -748,11 +785,12 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
   if (dq_status s = check_quantile_args("dq_approx_quantiles", type, cols, chunk_rows, n_chunks, quantiles, n_q,
                                         relative_error))
     return s;
+  if (dq_status s = check_selection("dq_approx_quantiles_where", selection, n_chunks)) return s;
   if (is_narrow(type)) {
     Widened w;
     if (dq_status s = widen(type, cols, chunk_rows, n_chunks, device, reinterpret_cast<hipStream_t>(hip_stream), w)) return s;
-    return dq_approx_quantiles(w.type, w.views.data(), chunk_rows, n_chunks, quantiles, n_q, relative_error, device,
-                               hip_stream, out, count);
+    return approx_quantiles_impl(w.type, w.views.data(), chunk_rows, selection, n_chunks, quantiles, n_q, relative_error,
+                                 device, hip_stream, out, count);
   }
   DQ_HIP(hipSetDevice(device));
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
@@ -849,6 +887,7 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
         const int64_t rows = chunk_rows[c];
         if (rows == 0) continue;
         const auto* val = reinterpret_cast<const uint32_t*>(cols[c].validity);
+        const auto* rs = selection ? reinterpret_cast<const uint32_t*>(selection[c]) : nullptr;
         const size_t lds = (size_t)nu * kQBins * sizeof(uint32_t) +
                            (append ? (size_t)nu * kQStage * 8 + (size_t)2 * nu * sizeof(uint32_t) : 0);
         const bool aligned = (reinterpret_cast<uintptr_t>(cols[c].values) & 15u) == 0;
@@ -859,14 +898,14 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
         const int sh = kQShift[pass];
         unsigned long long* const ao_p = pass == 0 ? d_andor : nullptr;
         if (type == DQ_TYPE_F64) {
-          if (aligned) launch_hist<DQ_TYPE_F64, 2>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
-          else launch_hist<DQ_TYPE_F64, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          if (aligned) launch_hist<DQ_TYPE_F64, 2>(append, grid, lds, stream, vals, val, rs, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          else launch_hist<DQ_TYPE_F64, 1>(append, grid, lds, stream, vals, val, rs, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
         } else if (type == DQ_TYPE_I64) {
-          if (aligned) launch_hist<DQ_TYPE_I64, 2>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
-          else launch_hist<DQ_TYPE_I64, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          if (aligned) launch_hist<DQ_TYPE_I64, 2>(append, grid, lds, stream, vals, val, rs, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          else launch_hist<DQ_TYPE_I64, 1>(append, grid, lds, stream, vals, val, rs, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
         } else {
-          if (aligned) launch_hist<DQ_TYPE_I32, 4>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
-          else launch_hist<DQ_TYPE_I32, 1>(append, grid, lds, stream, vals, val, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          if (aligned) launch_hist<DQ_TYPE_I32, 4>(append, grid, lds, stream, vals, val, rs, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
+          else launch_hist<DQ_TYPE_I32, 1>(append, grid, lds, stream, vals, val, rs, rows, sh, dmask32, nu, usel, dh.get(), ao_p);
         }
         DQ_HIP(hipGetLastError());
       }
@@ -928,19 +967,36 @@ dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const in
   return DQ_OK;
 }
 
-dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows, int32_t n_chunks,
-                             double relative_error, int32_t device, void* hip_stream, double* values, int64_t* ranks,
-                             int64_t cap, int64_t* n_samples, int64_t* count) {
+dq_status dq_approx_quantiles(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows, int32_t n_chunks,
+                              const double* quantiles, int32_t n_q, double relative_error, int32_t device,
+                              void* hip_stream, double* out, int64_t* count) {
+  return approx_quantiles_impl(type, cols, chunk_rows, nullptr, n_chunks, quantiles, n_q, relative_error, device,
+                               hip_stream, out, count);
+}
+
+dq_status dq_approx_quantiles_where(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows,
+                                    const uint64_t* const* selection, int32_t n_chunks, const double* quantiles,
+                                    int32_t n_q, double relative_error, int32_t device, void* hip_stream, double* out,
+                                    int64_t* count) {
+  return approx_quantiles_impl(type, cols, chunk_rows, selection, n_chunks, quantiles, n_q, relative_error, device,
+                               hip_stream, out, count);
+}
+
+static dq_status quantile_digest_impl(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows,
+                                      const uint64_t* const* selection, int32_t n_chunks, double relative_error,
+                                      int32_t device, void* hip_stream, double* values, int64_t* ranks, int64_t cap,
+                                      int64_t* n_samples, int64_t* count) {
   if (!cols || !chunk_rows || !n_samples || !count || n_chunks < 0 || cap < 0 || (cap > 0 && (!values || !ranks)))
     return set_error(DQ_E_INVALID, "dq_quantile_digest: NULL argument");
   if (dq_status s = check_quantile_args("dq_quantile_digest", type, cols, chunk_rows, n_chunks, nullptr, 0,
                                         relative_error))
     return s;
+  if (dq_status s = check_selection("dq_quantile_digest_where", selection, n_chunks)) return s;
   if (is_narrow(type)) {
     Widened w;
     if (dq_status s = widen(type, cols, chunk_rows, n_chunks, device, reinterpret_cast<hipStream_t>(hip_stream), w)) return s;
-    return dq_quantile_digest(w.type, w.views.data(), chunk_rows, n_chunks, relative_error, device, hip_stream, values,
-                              ranks, cap, n_samples, count);
+    return quantile_digest_impl(w.type, w.views.data(), chunk_rows, selection, n_chunks, relative_error, device,
+                                hip_stream, values, ranks, cap, n_samples, count);
   }
   int64_t total = 0;
   for (int c = 0; c < n_chunks; ++c) total += chunk_rows[c];
@@ -996,7 +1052,7 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
         const int64_t mc = s_off[(size_t)c + 1] - s_off[(size_t)c];
         hipLaunchKernelGGL((dq_digest_sample<decltype(tk)::value>), dim3((unsigned)((mc + kQBlock - 1) / kQBlock)),
                            dim3(kQBlock), 0, stream, cols[c].values, reinterpret_cast<const uint32_t*>(cols[c].validity),
-                           rows, mc, d_sample.p + s_off[(size_t)c], d_ok.p + s_off[(size_t)c]);
+                           selection ? reinterpret_cast<const uint32_t*>(selection[c]) : nullptr, rows, mc, d_sample.p + s_off[(size_t)c], d_ok.p + s_off[(size_t)c]);
       }))
     return st;
   // the sample sorted on the device (NULLs last; a host std::sort of 16384 keys took ~0.6-1 ms per digest, r6dg)
@@ -1020,9 +1076,12 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
   DQ_HIP(hipMemsetAsync(d_counts.p, 0, (size_t)2 * kDCountCopies * kDBuckets * 8, stream));
   // 2. per-bucket counts (and of each bucket's keys equal to its lower splitter)
   if (dq_status st = for_chunks([&](auto tk, int grid, int c, int64_t rows) {
-        hipLaunchKernelGGL((dq_digest_pass<decltype(tk)::value, true>), dim3(grid), dim3(kQBlock), 0, stream,
-                           cols[c].values, reinterpret_cast<const uint32_t*>(cols[c].validity), rows, d_spl.p, d_first,
-                           C, d_counts.p, nullptr, nullptr, nullptr, 0ull);
+        const auto* rs = selection ? reinterpret_cast<const uint32_t*>(selection[c]) : nullptr;
+        with_sel(rs != nullptr, [&](auto filtered) {
+          hipLaunchKernelGGL((dq_digest_pass<decltype(tk)::value, true, decltype(filtered)::value>), dim3(grid),
+                             dim3(kQBlock), 0, stream, cols[c].values, reinterpret_cast<const uint32_t*>(cols[c].validity),
+                             rs, rows, d_spl.p, d_first, C, d_counts.p, nullptr, nullptr, nullptr, 0ull);
+        });
       }))
     return st;
   std::vector<unsigned long long> cnt_copies((size_t)2 * kDCountCopies * kDBuckets), cnt((size_t)kDBuckets, 0),
@@ -1122,9 +1181,13 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
     hipLaunchKernelGGL(dq_digest_cursor_init, dim3(1), dim3(64), 0, stream, d_cursor.p);
     DQ_HIP(hipGetLastError());
     if (dq_status st = for_chunks([&](auto tk, int grid, int c, int64_t rows) {
-          hipLaunchKernelGGL((dq_digest_pass<decltype(tk)::value, false>), dim3(grid), dim3(kQBlock), 0, stream,
-                             cols[c].values, reinterpret_cast<const uint32_t*>(cols[c].validity), rows, d_spl.p,
-                             d_first, C, nullptr, d_target.p, cand, d_cursor.p, (unsigned long long)nc);
+          const auto* rs = selection ? reinterpret_cast<const uint32_t*>(selection[c]) : nullptr;
+          with_sel(rs != nullptr, [&](auto filtered) {
+            hipLaunchKernelGGL((dq_digest_pass<decltype(tk)::value, false, decltype(filtered)::value>), dim3(grid),
+                               dim3(kQBlock), 0, stream, cols[c].values,
+                               reinterpret_cast<const uint32_t*>(cols[c].validity), rs, rows, d_spl.p, d_first, C,
+                               nullptr, d_target.p, cand, d_cursor.p, (unsigned long long)nc);
+          });
         }))
       return st;
     // the candidates agree above their highest differing bit: sorting the bits below gives the full order
@@ -1167,6 +1230,21 @@ dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int
     ranks[i] = rank[(size_t)i];
   }
   return DQ_OK;
+}
+
+dq_status dq_quantile_digest(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows, int32_t n_chunks,
+                             double relative_error, int32_t device, void* hip_stream, double* values, int64_t* ranks,
+                             int64_t cap, int64_t* n_samples, int64_t* count) {
+  return quantile_digest_impl(type, cols, chunk_rows, nullptr, n_chunks, relative_error, device, hip_stream, values,
+                              ranks, cap, n_samples, count);
+}
+
+dq_status dq_quantile_digest_where(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows,
+                                   const uint64_t* const* selection, int32_t n_chunks, double relative_error,
+                                   int32_t device, void* hip_stream, double* values, int64_t* ranks, int64_t cap,
+                                   int64_t* n_samples, int64_t* count) {
+  return quantile_digest_impl(type, cols, chunk_rows, selection, n_chunks, relative_error, device, hip_stream, values,
+                              ranks, cap, n_samples, count);
 }
 
 }  // extern "C"

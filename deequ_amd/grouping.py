@@ -191,6 +191,67 @@ def _views(chunks, columns: Sequence[str]):
     return views, rows
 
 
+# times a `where` text was turned into per-chunk bitmaps (tests read it, as they read expressions.eval_calls)
+selection_builds = 0
+
+
+class Selection:
+    """The rows of a chunk list for which a `where` is TRUE: per chunk the device bitmap (64-bit words, LSB first: the
+    layout dq_take_index reads) and its number of set bits.  The data the filtered analyzers see is these rows."""
+
+    def __init__(self, where: str, bitmaps: Sequence, counts: Sequence[int]):
+        self.where, self.bitmaps, self.counts = where, list(bitmaps), [int(c) for c in counts]
+
+    @property
+    def num_rows(self) -> int:
+        return sum(self.counts)
+
+    def pointers(self):
+        """One selection pointer per chunk, as the _where entry points take them."""
+        return (ctypes.c_void_p * max(1, len(self.bitmaps)))(*[b.data_ptr() for b in self.bitmaps])
+
+
+def _where_columns(schema, where: str) -> set:
+    """The columns a `where` text names outside its arithmetic operands (host only)."""
+    from .analyzers import PlanBuilder
+
+    b = PlanBuilder([(n, "utf8" if dt == "dict_utf8" else dt, nl) for n, dt, nl in schema], collect_exprs=True)
+    b.pred(where)
+    return set(b.columns)
+
+
+def selection_of(data, where: Optional[str], analyzer=None, cache: Optional[dict] = None) -> Optional[Selection]:
+    """The Selection of `where` over `data` (None for no filter), through rowlevel.predicate_selection: arithmetic
+    operands and dictionary columns as the row-level checks handle them.  cache: a run's {where text: Selection} --
+    every analyzer of the run that carries the text shares one evaluation.  A text outside the GPU grammar raises the
+    UnsupportedOnGpuPathException the scan analyzers' failure metrics carry, a missing column what Compliance's
+    `where` fails with; both before anything is launched."""
+    if where is None:
+        return None
+    if cache is not None and where in cache:
+        return cache[where]
+    global selection_builds
+    from .metrics import NoSuchColumnException, UnsupportedOnGpuPathException
+    from .predicates import UnsupportedPredicate
+    from .rowlevel import predicate_selection
+    from .runner import _chunks
+
+    try:
+        pairs = predicate_selection(_chunks(data), where)
+    except UnsupportedPredicate as e:
+        raise UnsupportedOnGpuPathException(
+            f"{analyzer} is outside the GPU-eligible set ({e}); a Spark integration keeps it on data.agg") from e
+    except NoSuchColumnException as e:
+        if isinstance(e.__cause__, KeyError):  # the predicate compiler's own error: what Compliance fails with
+            raise e.__cause__
+        raise
+    selection_builds += 1
+    sel = Selection(where, [p[0] for p in pairs], [p[1] for p in pairs])
+    if cache is not None:
+        cache[where] = sel
+    return sel
+
+
 def index_path_dictionaries(chunks, columns: Sequence[str]):
     """The distinct Dictionary objects of a grouping that is computed on dictionary indices, else None.  The index
     path takes a grouping over exactly one column that is dict_utf8 in every chunk, when the distinct dictionaries
@@ -209,12 +270,13 @@ def index_path_dictionaries(chunks, columns: Sequence[str]):
     return dicts
 
 
-def _frequencies_from_indices(chunks, column: str, dicts) -> "FrequenciesAndNumRows":
+def _frequencies_from_indices(chunks, column: str, dicts, selection: Optional[Selection] = None) -> "FrequenciesAndNumRows":
     """The frequency table of a dictionary column without its strings' bytes per row: the rows of every chunk counted
     per entry (dq_dict_count, one int64 array per distinct dictionary), then dq_freq_build_weighted over the
     dictionaries' entries -- one input chunk per dictionary -- with those counts as weights.  Entries no row carries
     and NULL entries make no group, entries of equal bytes (in one dictionary or in two) make one.  The state's
-    representative rows point into the entries, which are its source tables."""
+    representative rows point into the entries, which are its source tables.  selection: only its rows are counted
+    (dq_dict_count_where) and numRows is their number."""
     import dataclasses
 
     import torch
@@ -224,30 +286,43 @@ def _frequencies_from_indices(chunks, column: str, dicts) -> "FrequenciesAndNumR
     dev = torch.cuda.current_device()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     counts = {id(d): torch.zeros(max(1, d.n_entries), dtype=torch.int64, device=d.entries.values.device) for d in dicts}
-    for t in chunks:
+    for k, t in enumerate(chunks):
         col = t.columns[column]
         view = col.view()
-        L.check(L.lib.dq_dict_count(ctypes.byref(view), t.num_rows, counts[id(col.dictionary)].data_ptr(), dev, stream))
+        if selection is None:
+            L.check(L.lib.dq_dict_count(ctypes.byref(view), t.num_rows, counts[id(col.dictionary)].data_ptr(), dev,
+                                        stream))
+        else:
+            L.check(L.lib.dq_dict_count_where(ctypes.byref(view), t.num_rows, selection.bitmaps[k].data_ptr(),
+                                              counts[id(col.dictionary)].data_ptr(), dev, stream))
     entry_chunks = [Table([dataclasses.replace(d.entries, name=column)]) for d in dicts]
     types = (ctypes.c_int32 * 1)(_gpu_type(dicts[0].entries.dtype))
     views, rows = _views(entry_chunks, [column])
     weights = (ctypes.c_void_p * len(dicts))(*[counts[id(d)].data_ptr() for d in dicts])
     h = ctypes.c_void_p()
     L.check(L.lib.dq_freq_build_weighted(types, 1, views, rows, weights, len(dicts), dev, stream, ctypes.byref(h)))
-    return FrequenciesAndNumRows(FreqTable(h, list(types)), sum(t.num_rows for t in chunks),
-                                 source=(entry_chunks, [column]))
+    num_rows = sum(t.num_rows for t in chunks) if selection is None else selection.num_rows
+    return FrequenciesAndNumRows(FreqTable(h, list(types)), num_rows, source=(entry_chunks, [column]))
 
 
-def build_frequencies(data, columns: Sequence[str]) -> "FrequenciesAndNumRows":
+def build_frequencies(data, columns: Sequence[str], where: Optional[str] = None, analyzer=None,
+                      selections: Optional[dict] = None) -> "FrequenciesAndNumRows":
     """computeFrequencies(data, columns) + numRows = data.count() on the GPU.  A single dictionary-encoded column is
-    grouped on its indices (index_path_dictionaries); the table is the one its decoded column gives."""
+    grouped on its indices (index_path_dictionaries); the table is the one its decoded column gives.
+    where: the frequencies and numRows of the rows for which the predicate is TRUE, as if the data held those rows
+    alone (dq_freq_build_where: the selection bitmaps join the validity in the kernels' row test; no column is
+    copied).  The index path is kept when the filter does not read the grouping column, and left when it does.
+    analyzer: named in the failure of a refused predicate; selections: a run's cache for selection_of."""
     from .runner import _chunks
     from .table import plain_utf8
 
     chunks = _chunks(data)
+    selection = selection_of(chunks, where, analyzer, selections)
     dicts = index_path_dictionaries(chunks, columns)
+    if dicts is not None and selection is not None and columns[0] in _where_columns(chunks[0].schema, where):
+        dicts = None
     if dicts is not None:
-        return _frequencies_from_indices(chunks, columns[0], dicts)
+        return _frequencies_from_indices(chunks, columns[0], dicts, selection)
     # a dictionary-encoded column among the grouping's own columns is read as the plain column it stands for; the
     # table's other dictionary columns are not touched
     chunks = plain_utf8(chunks, columns)
@@ -259,9 +334,14 @@ def build_frequencies(data, columns: Sequence[str]) -> "FrequenciesAndNumRows":
     h = ctypes.c_void_p()
     dev = torch.cuda.current_device()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(L.lib.dq_freq_build(types, len(columns), views, rows, len(chunks), dev, stream, ctypes.byref(h)))
-    return FrequenciesAndNumRows(FreqTable(h, list(types)), sum(t.num_rows for t in chunks),
-                                 source=(chunks, list(columns)))
+    if selection is None:
+        L.check(L.lib.dq_freq_build(types, len(columns), views, rows, len(chunks), dev, stream, ctypes.byref(h)))
+        num_rows = sum(t.num_rows for t in chunks)
+    else:
+        L.check(L.lib.dq_freq_build_where(types, len(columns), views, rows, selection.pointers(), len(chunks), dev,
+                                          stream, ctypes.byref(h)))
+        num_rows = selection.num_rows
+    return FrequenciesAndNumRows(FreqTable(h, list(types)), num_rows, source=(chunks, list(columns)))
 
 
 class FrequenciesAndNumRows(State):
@@ -314,14 +394,18 @@ class FrequencyBasedAnalyzer(Analyzer):
 
     grouping = True
 
-    def __init__(self, columns: Union[str, Sequence[str]]):
+    def __init__(self, columns: Union[str, Sequence[str]], where: Optional[str] = None):
         self.columns: List[str] = [columns] if isinstance(columns, str) else list(columns)
+        self.where = where
 
-    def _fields(self):
-        return (tuple(self.columns),)
+    def _fields(self):  # (an unfiltered analyzer's identity is the one it had before filters)
+        return (tuple(self.columns),) if self.where is None else (tuple(self.columns), ("where", self.where))
+
+    def _where_str(self) -> str:
+        return "" if self.where is None else f",Some({self.where})"
 
     def __str__(self):
-        return f"{type(self).__name__}(List({', '.join(self.columns)}))"
+        return f"{type(self).__name__}(List({', '.join(self.columns)}){self._where_str()})"
 
     __repr__ = __str__
 
@@ -343,7 +427,7 @@ class FrequencyBasedAnalyzer(Analyzer):
         return [at_least_one] + [Preconditions.hasColumn(c) for c in self.columns]
 
     def computeStateFrom(self, data) -> Optional[FrequenciesAndNumRows]:
-        return build_frequencies(data, self.columns)
+        return build_frequencies(data, self.columns, self.where, self)
 
     def _value(self, s: L.FreqSummary, num_rows: int) -> Optional[float]:
         raise NotImplementedError
@@ -405,11 +489,11 @@ class UniqueValueRatio(FrequencyBasedAnalyzer):  # UniqueValueRatio.scala:22-43
 class Entropy(FrequencyBasedAnalyzer):  # Entropy.scala:26-44 (single column)
     name = "Entropy"
 
-    def __init__(self, column: str):
-        super().__init__([column])
+    def __init__(self, column: str, where: Optional[str] = None):
+        super().__init__([column], where)
 
     def __str__(self):
-        return f"Entropy({self.columns[0]})"
+        return f"Entropy({self.columns[0]}{self._where_str()})"
 
     __repr__ = __str__
 
@@ -427,9 +511,10 @@ class MutualInformation(FrequencyBasedAnalyzer):  # MutualInformation.scala:32-8
     runOnAggregatedStates and loadStateAndComputeMetric."""
     name = "MutualInformation"
     direct = True
+    shares_selections = True  # calculate(..., selections=): the run's cache of `where` bitmaps (selection_of)
 
-    def __init__(self, columnA, columnB: Optional[str] = None):
-        super().__init__(list(columnA) if columnB is None else [columnA, columnB])
+    def __init__(self, columnA, columnB: Optional[str] = None, where: Optional[str] = None):
+        super().__init__(list(columnA) if columnB is None else [columnA, columnB], where)
 
     @property
     def entity(self):
@@ -441,12 +526,13 @@ class MutualInformation(FrequencyBasedAnalyzer):  # MutualInformation.scala:32-8
                 raise ValueError(f"{self.columns} has {len(self.columns)} columns, but exactly 2 are required")
         return [exactly_two] + [Preconditions.hasColumn(c) for c in self.columns]
 
-    def compute(self, data) -> DoubleMetric:
+    def compute(self, data, selections: Optional[dict] = None) -> DoubleMetric:
         import torch
 
         from .runner import _chunks
 
         chunks = _chunks(data)
+        selection = selection_of(chunks, self.where, self, selections)
         schema = {name: dt for name, dt, _ in chunks[0].schema}
         types = (ctypes.c_int32 * 2)(*[_gpu_type(schema[c]) for c in self.columns])
         views = (L.ColumnView * max(1, 2 * len(chunks)))()
@@ -457,20 +543,26 @@ class MutualInformation(FrequencyBasedAnalyzer):  # MutualInformation.scala:32-8
                 views[2 * k + c] = t.columns[name].view()
         value, defined = ctypes.c_double(), ctypes.c_int32()
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L.check(L.lib.dq_mutual_information(types, views, rows, len(chunks), sum(t.num_rows for t in chunks),
-                                            torch.cuda.current_device(), stream, ctypes.byref(value),
-                                            ctypes.byref(defined)))
+        if selection is None:
+            L.check(L.lib.dq_mutual_information(types, views, rows, len(chunks), sum(t.num_rows for t in chunks),
+                                                torch.cuda.current_device(), stream, ctypes.byref(value),
+                                                ctypes.byref(defined)))
+        else:
+            L.check(L.lib.dq_mutual_information_where(types, views, rows, selection.pointers(), len(chunks),
+                                                      selection.num_rows, torch.cuda.current_device(), stream,
+                                                      ctypes.byref(value), ctypes.byref(defined)))
         if not defined.value:
             return self._empty()
         return DoubleMetric(self.entity, self.name, self.instance, Success(value.value))
 
-    def calculate(self, data, aggregateWith=None, saveStatesWith=None) -> DoubleMetric:
+    def calculate(self, data, aggregateWith=None, saveStatesWith=None, selections: Optional[dict] = None) -> DoubleMetric:
         try:
             for cond in self.preconditions():
                 cond(data_schema(data))
             if aggregateWith is not None or saveStatesWith is not None:
-                return self.calculateMetric(self.computeStateFrom(data), aggregateWith, saveStatesWith)
-            return self.compute(data)
+                state = build_frequencies(data, self.columns, self.where, self, selections)
+                return self.calculateMetric(state, aggregateWith, saveStatesWith)
+            return self.compute(data, selections)
         except Exception as e:
             return self.toFailureMetric(e)
 
@@ -523,10 +615,12 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
     name = "Histogram"
     grouping = True
     direct = True
+    shares_selections = True
     NullFieldReplacement = "NullValue"
     MaximumAllowedDetailBins = 1000
 
-    def __init__(self, column: str, binningUdf=None, maxDetailBins: int = 1000, binning=None):
+    def __init__(self, column: str, binningUdf=None, maxDetailBins: int = 1000, binning=None, *,
+                 where: Optional[str] = None):
         from .binning import Bins
 
         if binning is not None and not isinstance(binning, Bins):
@@ -535,16 +629,20 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
         self.binningUdf = binningUdf
         self.maxDetailBins = maxDetailBins
         self.binning = binning
+        self.where = where
 
     def _fields(self):
         base = (self.column, id(self.binningUdf) if self.binningUdf is not None else None, self.maxDetailBins)
-        return base if self.binning is None else base + (self.binning,)
+        if self.binning is not None:
+            base += (self.binning,)
+        return base if self.where is None else base + (("where", self.where),)
 
     def __str__(self):
         udf = "None" if self.binningUdf is None else "Some(udf)"
+        w = "" if self.where is None else f",Some({self.where})"
         if self.binning is not None:
-            return f"Histogram({self.column},{udf},{self.maxDetailBins},{self.binning})"
-        return f"Histogram({self.column},{udf},{self.maxDetailBins})"
+            return f"Histogram({self.column},{udf},{self.maxDetailBins},{self.binning}{w})"
+        return f"Histogram({self.column},{udf},{self.maxDetailBins}{w})"
 
     __repr__ = __str__
 
@@ -642,7 +740,7 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
         values = {k: DistributionValue(c, c / state.numRows) for k, c in bins}
         return HistogramMetric(self.column, Success(Distribution(values, numberOfBins=bin_count)))
 
-    def calculate(self, data, aggregateWith=None, saveStatesWith=None):
+    def calculate(self, data, aggregateWith=None, saveStatesWith=None, selections: Optional[dict] = None):
         try:
             for cond in self.preconditions():
                 cond(data_schema(data))
@@ -654,9 +752,11 @@ class Histogram(Analyzer):  # Histogram.scala:33-99
                 from .binning import binned_frequencies
                 from .runner import _chunks
 
-                state = binned_frequencies(_chunks(data), self.column, self.binning)
+                chunks = _chunks(data)
+                state = binned_frequencies(chunks, self.column, self.binning,
+                                           selection_of(chunks, self.where, self, selections))
             else:
-                state = build_frequencies(data, [self.column])
+                state = build_frequencies(data, [self.column], self.where, self, selections)
             if aggregateWith is not None or saveStatesWith is not None:
                 state.materialize()  # once, before the merge and the first persist
             if aggregateWith is not None:

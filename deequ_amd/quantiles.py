@@ -36,8 +36,10 @@ def _param_msg(kind: str, v: float) -> str:  # MetricCalculationException.getApp
     return f"{kind} parameter must be in the closed interval [0, 1]. Currently, the value is: {_java_double_to_string(v)}!"
 
 
-def device_quantiles(data, column: str, quantiles: Sequence[float], relative_error: float) -> List[float] | None:
-    """dq_approx_quantiles over every chunk of `data`; None when all values are NULL."""
+def device_quantiles(data, column: str, quantiles: Sequence[float], relative_error: float,
+                     selection=None) -> List[float] | None:
+    """dq_approx_quantiles over every chunk of `data`; None when all values are NULL.  selection (a
+    grouping.Selection): over its rows only (dq_approx_quantiles_where)."""
     import torch
 
     from .runner import _chunks
@@ -58,9 +60,14 @@ def device_quantiles(data, column: str, quantiles: Sequence[float], relative_err
         res = (ctypes.c_double * len(part))()
         cnt = ctypes.c_int64()
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L.check(L.lib.dq_approx_quantiles(_gpu_type(schema[column]), views, rows, len(chunks), q, len(part),
-                                          float(relative_error), torch.cuda.current_device(), stream, res,
-                                          ctypes.byref(cnt)))
+        if selection is None:
+            L.check(L.lib.dq_approx_quantiles(_gpu_type(schema[column]), views, rows, len(chunks), q, len(part),
+                                              float(relative_error), torch.cuda.current_device(), stream, res,
+                                              ctypes.byref(cnt)))
+        else:
+            L.check(L.lib.dq_approx_quantiles_where(_gpu_type(schema[column]), views, rows, selection.pointers(),
+                                                    len(chunks), q, len(part), float(relative_error),
+                                                    torch.cuda.current_device(), stream, res, ctypes.byref(cnt)))
         n_total = cnt.value
         if n_total == 0:
             return None
@@ -231,13 +238,13 @@ def digest_ranks(n: int, relativeError: float) -> List[int]:
 MAX_DIGEST_SAMPLES = 1 << 20
 
 
-def device_digest(data, column: str, relativeError: float) -> PercentileDigest:
+def device_digest(data, column: str, relativeError: float, selection=None) -> PercentileDigest:
     """The column's digest from exact order statistics: dq_quantile_digest answers every sample rank in two
     passes over the column's non-null values on the device (per-bucket counts against sampled splitters, then
     the keys of the buckets that hold a sample rank compacted and sorted), whatever the number of samples; an
     empty digest (count 0) when every value is NULL."""
     rel = spark_relative_error(relativeError)
-    n, ranks, values = _digest_samples(data, column, rel)
+    n, ranks, values = _digest_samples(data, column, rel, selection)
     if n == 0:
         return PercentileDigest(QuantileSummaries(QuantileSummaries.defaultCompressThreshold, rel))
     assert ranks == digest_ranks(n, rel)[:len(ranks)] and ranks[-1] == n
@@ -248,8 +255,9 @@ def device_digest(data, column: str, relativeError: float) -> PercentileDigest:
     return PercentileDigest(QuantileSummaries(QuantileSummaries.defaultCompressThreshold, rel, sampled, n))
 
 
-def _digest_samples(data, column: str, rel: float):
-    """(n, sample ranks, sample values) of the column through dq_quantile_digest."""
+def _digest_samples(data, column: str, rel: float, selection=None):
+    """(n, sample ranks, sample values) of the column through dq_quantile_digest (selection: a grouping.Selection,
+    through dq_quantile_digest_where)."""
     import torch
 
     from .runner import _chunks
@@ -271,8 +279,14 @@ def _digest_samples(data, column: str, rel: float):
     rks = (ctypes.c_int64 * max(1, cap))()
     m, cnt = ctypes.c_int64(), ctypes.c_int64()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rc = L.lib.dq_quantile_digest(_gpu_type(schema[column]), views, rows, len(chunks), rel, torch.cuda.current_device(),
-                                  stream, vals, rks, cap, ctypes.byref(m), ctypes.byref(cnt))
+    if selection is None:
+        rc = L.lib.dq_quantile_digest(_gpu_type(schema[column]), views, rows, len(chunks), rel,
+                                      torch.cuda.current_device(), stream, vals, rks, cap, ctypes.byref(m),
+                                      ctypes.byref(cnt))
+    else:
+        rc = L.lib.dq_quantile_digest_where(_gpu_type(schema[column]), views, rows, selection.pointers(), len(chunks),
+                                            rel, torch.cuda.current_device(), stream, vals, rks, cap, ctypes.byref(m),
+                                            ctypes.byref(cnt))
     if rc == L.DQ_E_INVALID and m.value > cap:
         raise UnsupportedOnGpuPathException(
             f"a relativeError of {rel} over {cnt.value} values needs {m.value} samples in the quantile state "
@@ -314,6 +328,7 @@ def _rank_select(data, column: str):
 class _QuantileBase(Analyzer):
     grouping = True  # not part of the fused dq_plan scan: its own device passes
     direct = True
+    shares_selections = True  # calculate(..., selections=): the run's cache of `where` bitmaps
 
     def _quantiles(self) -> List[float]:
         raise NotImplementedError
@@ -334,26 +349,36 @@ class _QuantileBase(Analyzer):
     def _empty_exc(self):
         return EmptyStateException(f"Empty state for analyzer {self}, all input values were NULL.")
 
-    def compute(self, data):
+    where: Optional[str] = None
+
+    def _selection(self, data, selections: Optional[dict] = None):
+        from .grouping import selection_of
+
+        return selection_of(data, self.where, self, selections)
+
+    def _with_where(self, fields: tuple) -> tuple:  # (an unfiltered analyzer's identity is the one it had before)
+        return fields if self.where is None else fields + (("opt", self.where),)
+
+    def compute(self, data, selections: Optional[dict] = None):
         raise NotImplementedError
 
-    def computeStateFrom(self, data) -> Optional[ApproxQuantileState]:
+    def computeStateFrom(self, data, selections: Optional[dict] = None) -> Optional[ApproxQuantileState]:
         raise NotImplementedError
 
     def computeMetricFrom(self, state: Optional[ApproxQuantileState]):
         raise NotImplementedError
 
-    def calculate(self, data, aggregateWith=None, saveStatesWith=None):
+    def calculate(self, data, aggregateWith=None, saveStatesWith=None, selections: Optional[dict] = None):
         """Without a state round trip: the exact order statistics.  With aggregateWith / saveStatesWith:
         load -> merge -> persist -> metric over the digest (Analyzer.scala:107-128)."""
         try:
             for cond in self.preconditions():
                 cond(data_schema(data))
             if aggregateWith is None and saveStatesWith is None:
-                return self.compute(data)
+                return self.compute(data, selections)
             from .analyzers import merge
 
-            state = self.computeStateFrom(data)
+            state = self.computeStateFrom(data, selections)
             loaded = aggregateWith.load(self) if aggregateWith is not None else None
             merged = merge(state, loaded)
             if merged is not None and saveStatesWith is not None:
@@ -366,26 +391,28 @@ class _QuantileBase(Analyzer):
 class ApproxQuantile(_QuantileBase):  # ApproxQuantile.scala:49-103
     name = "ApproxQuantile"
 
-    def __init__(self, column: str, quantile: float, relativeError: float = 0.01):
+    def __init__(self, column: str, quantile: float, relativeError: float = 0.01, where: Optional[str] = None):
         self.column, self.quantile, self.relativeError = column, float(quantile), float(relativeError)
+        self.where = where
 
     def _fields(self):
-        return (self.column, self.quantile, self.relativeError)
+        return self._with_where((self.column, self.quantile, self.relativeError))
 
     def _show(self):
-        return (self.column, _java_double_to_string(self.quantile), _java_double_to_string(self.relativeError))
+        return self._with_where((self.column, _java_double_to_string(self.quantile),
+                                 _java_double_to_string(self.relativeError)))
 
     def _quantiles(self):
         return [self.quantile]
 
-    def compute(self, data) -> DoubleMetric:
-        r = device_quantiles(data, self.column, [self.quantile], self.relativeError)
+    def compute(self, data, selections: Optional[dict] = None) -> DoubleMetric:
+        r = device_quantiles(data, self.column, [self.quantile], self.relativeError, self._selection(data, selections))
         if r is None:
             return self.toFailureMetric(self._empty_exc())
         return DoubleMetric(Entity.Column, self.name, self.column, Success(r[0]))
 
-    def computeStateFrom(self, data) -> Optional[ApproxQuantileState]:
-        digest = device_digest(data, self.column, self.relativeError)
+    def computeStateFrom(self, data, selections: Optional[dict] = None) -> Optional[ApproxQuantileState]:
+        digest = device_digest(data, self.column, self.relativeError, self._selection(data, selections))
         if not digest.getPercentiles([self.quantile]):  # all values NULL (ApproxQuantile.scala:72-77)
             return None
         return ApproxQuantileState(digest)
@@ -403,23 +430,25 @@ class ApproxQuantile(_QuantileBase):  # ApproxQuantile.scala:49-103
 class ApproxQuantiles(_QuantileBase):  # ApproxQuantiles.scala:30-105
     name = "ApproxQuantiles"
 
-    def __init__(self, column: str, quantiles: Sequence[float], relativeError: float = 0.01):
+    def __init__(self, column: str, quantiles: Sequence[float], relativeError: float = 0.01,
+                 where: Optional[str] = None):
         self.column, self.quantiles, self.relativeError = column, tuple(float(q) for q in quantiles), float(relativeError)
+        self.where = where
 
     def _fields(self):
-        return (self.column, self.quantiles, self.relativeError)
+        return self._with_where((self.column, self.quantiles, self.relativeError))
 
     def _show(self):
-        return (self.column, "List(" + ", ".join(_java_double_to_string(q) for q in self.quantiles) + ")",
-                _java_double_to_string(self.relativeError))
+        return self._with_where((self.column, "List(" + ", ".join(_java_double_to_string(q) for q in self.quantiles) + ")",
+                                 _java_double_to_string(self.relativeError)))
 
     def _quantiles(self):
         return list(self.quantiles)
 
-    def compute(self, data) -> KeyedDoubleMetric:
+    def compute(self, data, selections: Optional[dict] = None) -> KeyedDoubleMetric:
         if not self.quantiles:  # getPercentiles(Array()) -> an empty map
             return KeyedDoubleMetric(Entity.Column, self.name, self.column, Success({}))
-        r = device_quantiles(data, self.column, self.quantiles, self.relativeError)
+        r = device_quantiles(data, self.column, self.quantiles, self.relativeError, self._selection(data, selections))
         if r is None:
             # all values NULL: the digest is still Some (ApproxQuantiles.scala:64-72, no isEmpty check as in
             # ApproxQuantile.scala:72-77) and Spark 2.2's PercentileDigest.getPercentiles returns an empty
@@ -428,9 +457,9 @@ class ApproxQuantiles(_QuantileBase):  # ApproxQuantiles.scala:30-105
         vals: Dict[str, float] = {_java_double_to_string(q): v for q, v in zip(self.quantiles, r)}
         return KeyedDoubleMetric(Entity.Column, self.name, self.column, Success(vals))
 
-    def computeStateFrom(self, data) -> ApproxQuantileState:
+    def computeStateFrom(self, data, selections: Optional[dict] = None) -> ApproxQuantileState:
         # no emptiness check (ApproxQuantiles.scala:61-72): an all-NULL column is a digest of count 0
-        return ApproxQuantileState(device_digest(data, self.column, self.relativeError))
+        return ApproxQuantileState(device_digest(data, self.column, self.relativeError, self._selection(data, selections)))
 
     def computeMetricFrom(self, state: Optional[ApproxQuantileState]) -> KeyedDoubleMetric:
         if state is None:

@@ -338,6 +338,15 @@ _COLUMNS_ANALYZERS = {"CountDistinct": CountDistinct, "Distinctness": Distinctne
 
 
 def serialize_analyzer(analyzer: Analyzer) -> dict:  # AnalyzerSerializer (AnalysisResultSerde.scala:220-347)
+    node = _serialize_analyzer(analyzer)
+    # the grouping, histogram and quantile analyzers' filter: a "where" member only when one is set, so an unfiltered
+    # analyzer's JSON is the reference's
+    if "where" not in node and getattr(analyzer, "where", None) is not None:
+        node["where"] = analyzer.where
+    return node
+
+
+def _serialize_analyzer(analyzer: Analyzer) -> dict:
     t = type(analyzer)
     if t is Size:
         return {"analyzerName": "Size", "where": analyzer.where}
@@ -394,23 +403,23 @@ def deserialize_analyzer(node: dict) -> Analyzer:  # AnalyzerDeserializer (:349-
     if name in _WHERE_ANALYZERS:
         return _WHERE_ANALYZERS[name](node["column"], where)
     if name == "Entropy":
-        return Entropy(node["column"])
+        return Entropy(node["column"], where)
     if name in _COLUMNS_ANALYZERS:
-        return _COLUMNS_ANALYZERS[name](list(node["columns"]))
+        return _COLUMNS_ANALYZERS[name](list(node["columns"]), where=where)
     if name == "Histogram":
         binning = None
         if node.get("binning") is not None:
             from .binning import bins_from_json
 
             binning = bins_from_json(node["binning"])
-        return Histogram(node["column"], None, int(node["maxDetailBins"]), binning)
+        return Histogram(node["column"], None, int(node["maxDetailBins"]), binning, where=where)
     if name == "Correlation":
         return Correlation(node["firstColumn"], node["secondColumn"], where)
     if name == "ApproxQuantile":
-        return ApproxQuantile(node["column"], float(node["quantile"]), float(node["relativeError"]))
+        return ApproxQuantile(node["column"], float(node["quantile"]), float(node["relativeError"]), where)
     if name == "ApproxQuantiles":
         return ApproxQuantiles(node["column"], [float(q) for q in node["quantiles"].split(",")],
-                               float(node["relativeError"]))
+                               float(node["relativeError"]), where)
     if name == "ReferentialIntegrity":
         return ReferentialIntegrity(list(node["columns"]), StoredKeySet(int(node["numKeys"])), where)
     raise ValueError(f"Unable to deserialize analyzer {name}.")

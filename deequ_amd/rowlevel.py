@@ -51,7 +51,8 @@ def max_outputs() -> int:
 @dataclass(frozen=True)
 class RowForm:
     """The row-level form of one constraint.  kind "predicate": pred = ("sql", text) or ("regex", column, pattern),
-    where = the `where` text or None.  kind "unique": columns = the grouping columns.  kind "contains": analyzer =
+    where = the `where` text or None.  kind "unique": columns = the grouping columns, where = the analyzer's filter
+    (a selected row passes iff its tuple is unique among the selected rows).  kind "contains": analyzer =
     the ReferentialIntegrity analyzer (its columns, key set and `where`)."""
     key: str
     kind: str
@@ -84,7 +85,7 @@ def row_form(constraint) -> Union[RowForm, str]:
     if isinstance(analyzer, Compliance):
         return RowForm(key, "predicate", ("sql", analyzer.predicate), analyzer.where)
     if isinstance(analyzer, Uniqueness):
-        return RowForm(key, "unique", columns=tuple(analyzer.groupingColumns()))
+        return RowForm(key, "unique", where=analyzer.where, columns=tuple(analyzer.groupingColumns()))
     if isinstance(analyzer, ReferentialIntegrity):
         return RowForm(key, "contains", where=analyzer.where, columns=tuple(analyzer.columns), analyzer=analyzer)
     return f"{type(analyzer).__name__} has no row-level form"
@@ -248,7 +249,7 @@ def _sql_texts(checks) -> List[str]:
                 continue
             if f.kind == "predicate":
                 out += [r[1] for r in f.roots() if r[0] == "sql"]
-            elif f.kind == "contains" and f.where is not None:
+            elif f.kind in ("contains", "unique") and f.where is not None:
                 out.append(f.where)
     return list(dict.fromkeys(out))
 
@@ -282,6 +283,15 @@ def plan_row_level(checks, schema, max_outputs_per_program: Optional[int] = None
                     if missing:
                         skipped.append((key, f"NoSuchColumnException: Input data does not include column {missing[0]}!"))
                         continue
+                    if f.where is not None:  # its `where` runs as a row program of its own (predicate_selection)
+                        try:
+                            RowProgram([RowForm(key, "predicate", ("sql", f.where))], schema, expr_columns).close()
+                        except UnsupportedPredicate as e:
+                            skipped.append((key, f"UnsupportedPredicate: {e}"))
+                            continue
+                        except NoSuchColumnException as e:
+                            skipped.append((key, f"NoSuchColumnException: {e}"))
+                            continue
                 elif f.kind == "contains":
                     from .analyzers import Preconditions
 
@@ -462,14 +472,19 @@ def _and_outcomes(name: str, parts: List[RowOutcome], chunks: List[Table]) -> Ro
     return RowOutcome(name, out)
 
 
-def _unique_outcome(form: RowForm, chunks: List[Table]) -> RowOutcome:
+def _unique_outcome(form: RowForm, chunks: List[Table], null_mode: bool = False) -> RowOutcome:
+    """pass = the row's tuple occurs once (among the selected rows, under a `where`: the frequencies are built from
+    them and dq_freq_unique_rows_where leaves the unselected rows' bits 0); applies = the `where` bitmap."""
     import torch
 
+    from .grouping import selection_of
+
     cols = list(form.columns)
-    state = build_frequencies(chunks, cols)
+    selection = selection_of(chunks, form.where, form.key)
+    state = build_frequencies(chunks, cols, form.where, form.key, None if selection is None else {form.where: selection})
     probe = plain_utf8(chunks, cols)
     out = []
-    for t in probe:
+    for k, t in enumerate(probe):
         n, words = t.num_rows, (t.num_rows + 63) // 64
         dev = t.columns[cols[0]].values.device
         bitmap = torch.zeros((words + 1) * 8, dtype=torch.uint8, device=dev)
@@ -478,9 +493,17 @@ def _unique_outcome(form: RowForm, chunks: List[Table]) -> RowOutcome:
         nu = ctypes.c_int64(0)
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            L.check(L.lib.dq_freq_unique_rows(state.frequencies.handle, types, views, n, bitmap.data_ptr(), None, stream,
-                                              ctypes.byref(nu), None))
-        out.append(ChunkOutcome(bitmap, None, nu.value, n, n))
+            if selection is None:
+                L.check(L.lib.dq_freq_unique_rows(state.frequencies.handle, types, views, n, bitmap.data_ptr(), None,
+                                                  stream, ctypes.byref(nu), None))
+            else:
+                L.check(L.lib.dq_freq_unique_rows_where(state.frequencies.handle, types, views, n,
+                                                        selection.bitmaps[k].data_ptr(), bitmap.data_ptr(), None,
+                                                        stream, ctypes.byref(nu), None))
+        if selection is None:
+            out.append(ChunkOutcome(bitmap, None, nu.value, n, n))
+        else:
+            out.append(_filtered_outcome(bitmap, selection.bitmaps[k], nu.value, selection.counts[k], n, null_mode))
     return RowOutcome(form.key, out)
 
 
@@ -529,6 +552,11 @@ def predicate_bitmaps(chunks: List[Table], text: str) -> list:
     """Per chunk the bitmap of the rows for which the SQL predicate `text` is TRUE: a one-output row program, its
     arithmetic operands and dictionary columns handled as row_level_results handles them (_prepared).  A text outside
     the GPU grammar raises UnsupportedPredicate."""
+    return [p[0] for p in predicate_selection(chunks, text)]
+
+
+def predicate_selection(chunks: List[Table], text: str) -> list:
+    """predicate_bitmaps with each bitmap's number of set bits: per chunk (bitmap, rows for which `text` is TRUE)."""
     form = RowForm(text, "predicate", ("sql", text))
 
     def compile_one(schema, expr_columns):
@@ -537,7 +565,8 @@ def predicate_bitmaps(chunks: List[Table], text: str) -> list:
 
     pred_chunks, prog = _prepared(chunks, [text], compile_one)
     try:
-        return [prog.evaluate(t, [False])[0][0] for t in pred_chunks]
+        res = [prog.evaluate(t, [False])[0] for t in pred_chunks]
+        return [(r[0], r[2]) for r in res]
     finally:
         prog.close()
 
@@ -574,7 +603,8 @@ def row_level_results(checks, data, filteredRow: str = "TRUE") -> RowLevelResult
             prog.close()
     for key, f in plan.forms.items():
         if f.kind == "unique":
-            constraints[key] = _unique_outcome(f, chunks)
+            # (a filtered one reads the chunks that carry its `where`'s derived columns)
+            constraints[key] = _unique_outcome(f, chunks if f.where is None else pred_chunks, null_mode)
         elif f.kind == "contains":
             constraints[key] = _contains_outcome(f, pred_chunks, null_mode)  # (its `where`'s derived columns)
     per_check = {desc: _and_outcomes(desc, [constraints[k] for k in keys], chunks) for desc, keys in plan.checks}

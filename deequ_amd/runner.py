@@ -416,23 +416,33 @@ class AnalysisRunner:
         scanning = [a for a in passed if not getattr(a, "grouping", False)]
         ctx = AnalysisRunner.runScanningAnalyzers(data, scanning, aggregateWith, saveStatesWith)
         by_cols: Dict[tuple, List[Analyzer]] = {}
-        for a in grouping:  # AnalysisRunner.scala:160-180: one frequency computation per column set
-            if getattr(a, "direct", False):  # MutualInformation: its own device pass
-                ctx = ctx + AnalyzerContext({a: a.calculate(data, aggregateWith, saveStatesWith)})
+        # each distinct `where` text of the grouping, histogram and quantile analyzers becomes bitmaps once for this
+        # run's chunks (grouping.selection_of), shared by every analyzer that carries it
+        selections: Dict[str, object] = {}
+        for a in grouping:  # AnalysisRunner.scala:160-180: one frequency computation per column set and filter
+            if getattr(a, "direct", False):  # MutualInformation, Histogram, the quantiles: their own device passes
+                if getattr(a, "shares_selections", False) and a.where is not None:
+                    m = a.calculate(data, aggregateWith, saveStatesWith, selections=selections)
+                else:
+                    m = a.calculate(data, aggregateWith, saveStatesWith)
+                ctx = ctx + AnalyzerContext({a: m})
                 continue
-            by_cols.setdefault(tuple(a.groupingColumns()), []).append(a)
-        for cols, group in by_cols.items():
-            ctx = ctx + AnalysisRunner.runGroupingAnalyzers(data, list(cols), group, aggregateWith, saveStatesWith)
+            by_cols.setdefault((tuple(a.groupingColumns()), getattr(a, "where", None)), []).append(a)
+        for (cols, where), group in by_cols.items():
+            ctx = ctx + AnalysisRunner.runGroupingAnalyzers(data, list(cols), group, aggregateWith, saveStatesWith,
+                                                            where=where, selections=selections)
         return AnalyzerContext(failures) + ctx
 
     @staticmethod
-    def runGroupingAnalyzers(data, columns, analyzers, aggregateWith=None, saveStatesWith=None) -> AnalyzerContext:
+    def runGroupingAnalyzers(data, columns, analyzers, aggregateWith=None, saveStatesWith=None, where=None,
+                             selections=None) -> AnalyzerContext:
         """AnalysisRunner.scala:249-277 and runAnalyzersForParticularGrouping: frequencies once (GPU),
-        the state of the first analyzer merged with a loaded one, persisted for every analyzer."""
+        the state of the first analyzer merged with a loaded one, persisted for every analyzer.  where: the filter the
+        analyzers share (the frequencies of its rows alone); selections: the run's cache of filters' bitmaps."""
         from .grouping import build_frequencies
 
         try:
-            state = build_frequencies(data, columns)
+            state = build_frequencies(data, columns, where, analyzers[0], selections)
             if aggregateWith is not None:
                 prev = aggregateWith.load(analyzers[0])
                 if prev is not None:

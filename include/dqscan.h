@@ -47,7 +47,10 @@ extern "C" {
                                 predicates: DQ_PRED_EXPR, dq_pred_pool_num_exprs / _expr, dq_expr_eval / _host; uploads into
                                 caller-owned buffers: dq_upload_to / _payload / _stage; referential integrity:
                                 dq_freq_contains_rows (the rows whose tuple is a group of another table's key set);
-                                binned histograms: dq_bins_create / _destroy, dq_bin_count */
+                                binned histograms: dq_bins_create / _destroy, dq_bin_count; row selections for the grouping,
+                                histogram and quantile entry points: dq_freq_build_where / _unique_rows_where,
+                                dq_dict_count_where, dq_bin_count_where, dq_approx_quantiles_where,
+                                dq_quantile_digest_where, dq_mutual_information_where */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -942,6 +945,48 @@ dq_status dq_freq_top(const dq_freq_table* t, int32_t n, uint64_t* keys, int64_t
 dq_status dq_mutual_information(const int32_t* types, const dq_column_view* cols, const int64_t* chunk_rows,
                                 int32_t n_chunks, int64_t num_rows, int32_t device, void* hip_stream, double* value,
                                 int32_t* defined);
+
+/* ---- Row selections (`where`) for the grouping, histogram and quantile entry points (additions under ABI 6) ----
+ * X_where(..., selection, ...) is X over the data that holds exactly the selected rows, in their order: an unselected
+ * row is no part of the data -- it makes no group, is in no slot, has no rank, and does not count as a NULL either.
+ * A selection is a device bitmap of ceil(n_rows / 64) uint64_t words, LSB first, 8-byte aligned: the layout
+ * dq_take_index reads and dq_row_outcomes writes.  Bits past n_rows are ignored.  A NULL selection means every row
+ * (the unfiltered kernel runs); a misaligned one is DQ_E_INVALID before any launch.  Where the entry point takes
+ * chunks, `selection` is an array of n_chunks such pointers (host array, each entry NULL or a device bitmap), or NULL
+ * for no selection at all.  No entry point copies the selected values out: the selection joins the validity in the
+ * row test of the first pass, and everything after it sees selected rows only.
+ * dq_freq_build_where: dq_freq_build; the representative row ids are ids into the caller's unfiltered chunks, so
+ * dq_freq_materialize / _top / _take_values / _unique_rows_where take the same chunks.  The caller passes the number
+ * of selected rows, not the chunks', to dq_freq_summarize.
+ * dq_freq_unique_rows_where: unique / grouped bits of unselected rows are 0; the table is one built with the same
+ * selection (or from data that holds the selected rows).
+ * dq_dict_count_where / dq_bin_count_where: selection is the one chunk's bitmap.  *n_selected of dq_bin_count_where
+ * (device int64, 8-byte aligned, NULL: not wanted) ACCUMULATES the number of selected rows, NULL rows included, as
+ * counts accumulates; with a NULL selection it adds n_rows.
+ * dq_approx_quantiles_where / dq_quantile_digest_where: ranks and *count run over the selected non-null values.
+ * dq_mutual_information_where: num_rows is the number of selected rows. */
+dq_status dq_freq_build_where(const int32_t* types, int32_t n_cols, const dq_column_view* cols, const int64_t* chunk_rows,
+                              const uint64_t* const* selection, int32_t n_chunks, int32_t device, void* hip_stream,
+                              dq_freq_table** out);
+dq_status dq_freq_unique_rows_where(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols,
+                                    int64_t n_rows, const uint64_t* selection, uint64_t* unique, uint64_t* grouped,
+                                    void* hip_stream, int64_t* num_unique, int64_t* num_grouped);
+dq_status dq_dict_count_where(const dq_column_view* indices, int64_t n_rows, const uint64_t* selection, int64_t* counts,
+                              int32_t device, void* hip_stream);
+dq_status dq_bin_count_where(const dq_bins* bins, int32_t type, const dq_column_view* col, int64_t n_rows,
+                             const uint64_t* selection, int64_t* counts, int64_t* n_selected, int32_t device,
+                             void* hip_stream);
+dq_status dq_approx_quantiles_where(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows,
+                                    const uint64_t* const* selection, int32_t n_chunks, const double* quantiles,
+                                    int32_t n_q, double relative_error, int32_t device, void* hip_stream, double* out,
+                                    int64_t* count);
+dq_status dq_quantile_digest_where(int32_t type, const dq_column_view* cols, const int64_t* chunk_rows,
+                                   const uint64_t* const* selection, int32_t n_chunks, double relative_error,
+                                   int32_t device, void* hip_stream, double* values, int64_t* ranks, int64_t cap,
+                                   int64_t* n_samples, int64_t* count);
+dq_status dq_mutual_information_where(const int32_t* types, const dq_column_view* cols, const int64_t* chunk_rows,
+                                      const uint64_t* const* selection, int32_t n_chunks, int64_t num_rows,
+                                      int32_t device, void* hip_stream, double* value, int32_t* defined);
 
 /* State algebra.
  * dq_state_merge:   Analyzers.merge / State.sum on Option[State] (Analyzer.scala:343-362):
