@@ -335,6 +335,13 @@ def _load():
     L.dq_freq_contains_rows.restype = c.c_int32
     L.dq_freq_contains_rows.argtypes = [c.c_void_p, P(c.c_int32), P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p,
                                         c.c_void_p, c.c_void_p, P(c.c_int64), P(c.c_int64)]
+    L.dq_freq_lookup_rows.restype = c.c_int32
+    L.dq_freq_lookup_rows.argtypes = [c.c_void_p, P(c.c_int32), P(ColumnView), c.c_int64, c.c_void_p, c.c_void_p,
+                                      c.c_void_p, P(c.c_int64)]
+    L.dq_rows_match.restype = c.c_int32
+    L.dq_rows_match.argtypes = [P(c.c_int32), P(ColumnView), P(c.c_int32), P(ColumnView), c.c_int32, c.c_int64,
+                                c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32,
+                                c.c_void_p, P(c.c_int64), P(c.c_int64), P(c.c_int64), P(c.c_int64)]
     L.dq_split_rows.restype = c.c_int32
     L.dq_split_rows.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_double, c.c_void_p, c.c_void_p, c.c_int32,
                                 c.c_void_p, P(c.c_int64), P(c.c_int64)]
@@ -495,7 +502,7 @@ EXPORTED = [
     "dq_dict_count", "dq_freq_build_weighted", "dq_bins_create", "dq_bins_destroy", "dq_bin_count",
     "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
     "dq_row_max_outputs", "dq_row_program_create", "dq_row_program_info", "dq_row_program_destroy", "dq_row_outcomes",
-    "dq_freq_unique_rows", "dq_freq_contains_rows",
+    "dq_freq_unique_rows", "dq_freq_contains_rows", "dq_freq_lookup_rows", "dq_rows_match",
     "dq_freq_build_where", "dq_freq_unique_rows_where", "dq_dict_count_where", "dq_bin_count_where",
     "dq_approx_quantiles_where", "dq_quantile_digest_where", "dq_mutual_information_where",
     "dq_pred_pool_num_exprs", "dq_pred_pool_expr", "dq_expr_eval", "dq_expr_eval_host",

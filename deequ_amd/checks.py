@@ -20,7 +20,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
 from .analyzers import DataType, DataTypeInstances
 from .grouping import (Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
-from .matching import ReferentialIntegrity
+from .matching import DatasetMatch, ReferentialIntegrity
 from .quantiles import ApproxQuantile
 from .runner import AnalysisRunner, AnalyzerContext, arrow_data
 
@@ -293,6 +293,14 @@ class Check:  # Check.scala:59-902
         a NULL in a key column is not contained.  (Upstream: Check.doesDatasetMatch / ReferentialIntegrity.)"""
         return self._filterable(lambda w: _named(ReferentialIntegrity(columns, reference, w), assertion,
                                                  "ReferentialIntegrityConstraint", None, hint))
+
+    def doesDatasetMatch(self, keyColumns, compareColumns, reference, assertion=_is_one, hint=None):
+        """The fraction of rows that equal `reference`'s row with the same key (a matching.KeyedRows) meets the
+        assertion: key column k against key k of the reference, compareColumns (names on both sides, a dict
+        {column: reference column}, or None for every payload column) null-safe equal.  (Upstream:
+        Check.doesDatasetMatch with matchColumnMappings.)"""
+        return self._filterable(lambda w: _named(DatasetMatch(keyColumns, compareColumns, reference, w), assertion,
+                                                 "DatasetMatchConstraint", None, hint))
 
     # ---- constraints on the grouping, histogram and quantile analyzers: filterable, the `where` is the analyzer's ----
     def isUnique(self, column, hint=None):  # Check.scala:139-141

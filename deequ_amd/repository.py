@@ -24,7 +24,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
                         Mean, MinLength, Minimum, PatternMatch, Size, StandardDeviation, Sum)
 from .grouping import (CountDistinct, Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
-from .matching import ReferentialIntegrity, StoredKeySet
+from .matching import DatasetMatch, ReferentialIntegrity, StoredKeyedRows, StoredKeySet
 from .metrics import (Distribution, DistributionValue, DoubleMetric, Entity, Failure, HistogramMetric,
                       KeyedDoubleMetric, MetricCalculationRuntimeException, Success)
 from .quantiles import ApproxQuantile, ApproxQuantiles
@@ -388,6 +388,11 @@ def _serialize_analyzer(analyzer: Analyzer) -> dict:
         # only its size: the analyzer comes back able to key stored metrics and refusing to run (StoredKeySet)
         return {"analyzerName": "ReferentialIntegrity", "columns": list(analyzer.columns), "where": analyzer.where,
                 "numKeys": int(analyzer.reference.num_keys)}
+    if t is DatasetMatch:
+        # (no upstream layout either.)  The reference's rows are not stored, only its number of keys (StoredKeyedRows)
+        return {"analyzerName": "DatasetMatch", "keyColumns": list(analyzer.keyColumns),
+                "compareColumns": [[c, rc] for c, rc in analyzer.mapping or ()], "where": analyzer.where,
+                "numKeys": int(analyzer.reference.num_keys)}
     raise ValueError(f"Unable to serialize analyzer {analyzer}.")
 
 
@@ -422,6 +427,9 @@ def deserialize_analyzer(node: dict) -> Analyzer:  # AnalyzerDeserializer (:349-
                                float(node["relativeError"]), where)
     if name == "ReferentialIntegrity":
         return ReferentialIntegrity(list(node["columns"]), StoredKeySet(int(node["numKeys"])), where)
+    if name == "DatasetMatch":
+        return DatasetMatch(list(node["keyColumns"]), [tuple(m) for m in node["compareColumns"]],
+                            StoredKeyedRows(int(node["numKeys"])), where)
     raise ValueError(f"Unable to deserialize analyzer {name}.")
 
 

@@ -10,10 +10,12 @@ upstream: a row passes when the thing the metric counts holds for it.
   PatternMatch (hasPattern, ...)    regexp_extract(col, pattern, 0) != '' (a NULL value fails, as the metric counts it)
   Uniqueness (isUnique, ...)        the row's group has count 1 (a NULL key column: not unique)
   ReferentialIntegrity              the row's tuple is a key of the reference key set (a NULL key column: not contained)
+  DatasetMatch                      the row equals the reference's row with the same key (a missing key: no match)
 
 The first three run as row programs (dq_row_program_create / dq_row_outcomes: the predicate pass that stores rows
 instead of counting them); Uniqueness probes the grouping's frequency table (dq_freq_unique_rows) and
-ReferentialIntegrity the reference's key set (dq_freq_contains_rows, its `where` bitmap as the filter).  Every other
+ReferentialIntegrity the reference's key set (dq_freq_contains_rows, its `where` bitmap as the filter); DatasetMatch
+looks its rows up there and compares them with the reference's (dq_freq_lookup_rows + dq_rows_match).  Every other
 constraint has no row-level form and is listed in `skipped` with the reason; for a check's AND it counts as passing.
 A predicate outside the GPU grammar is skipped the same way, with the compiler's reason -- never dropped silently.
 
@@ -35,7 +37,7 @@ import numpy as np
 from . import _lib as L
 from .analyzers import Completeness, Compliance, PatternMatch, PlanBuilder
 from .grouping import Uniqueness, _gpu_type, build_frequencies
-from .matching import ReferentialIntegrity
+from .matching import DatasetMatch, ReferentialIntegrity
 from .metrics import NoSuchColumnException
 from .predicates import UnsupportedPredicate
 from .table import Table, plain_utf8
@@ -53,7 +55,8 @@ class RowForm:
     """The row-level form of one constraint.  kind "predicate": pred = ("sql", text) or ("regex", column, pattern),
     where = the `where` text or None.  kind "unique": columns = the grouping columns, where = the analyzer's filter
     (a selected row passes iff its tuple is unique among the selected rows).  kind "contains": analyzer =
-    the ReferentialIntegrity analyzer (its columns, key set and `where`)."""
+    the ReferentialIntegrity analyzer (its columns, key set and `where`) or the DatasetMatch analyzer (pass = matched:
+    the failing rows are the missing and the different ones)."""
     key: str
     kind: str
     pred: Optional[tuple] = None
@@ -88,6 +91,9 @@ def row_form(constraint) -> Union[RowForm, str]:
         return RowForm(key, "unique", where=analyzer.where, columns=tuple(analyzer.groupingColumns()))
     if isinstance(analyzer, ReferentialIntegrity):
         return RowForm(key, "contains", where=analyzer.where, columns=tuple(analyzer.columns), analyzer=analyzer)
+    if isinstance(analyzer, DatasetMatch):
+        return RowForm(key, "contains", where=analyzer.where, columns=tuple(analyzer.groupingColumns()),
+                       analyzer=analyzer)
     return f"{type(analyzer).__name__} has no row-level form"
 
 
@@ -519,7 +525,8 @@ def _filtered_outcome(p, a, npass: int, napp: int, n: int, null_mode: bool) -> C
 
 
 def _contains_outcome(form: RowForm, chunks: List[Table], null_mode: bool) -> RowOutcome:
-    """pass = contained, applies = the `where` bitmap: one dq_freq_contains_rows per chunk."""
+    """pass = contained (DatasetMatch: matched), applies = the `where` bitmap: one dq_freq_contains_rows (one
+    dq_freq_lookup_rows and one dq_rows_match) per chunk."""
     res = form.analyzer.probe(chunks, want_applies=form.where is not None)
     return RowOutcome(form.key, [_filtered_outcome(*r, t.num_rows, null_mode) for t, r in zip(chunks, res)])
 

@@ -50,7 +50,9 @@ extern "C" {
                                 binned histograms: dq_bins_create / _destroy, dq_bin_count; row selections for the grouping,
                                 histogram and quantile entry points: dq_freq_build_where / _unique_rows_where,
                                 dq_dict_count_where, dq_bin_count_where, dq_approx_quantiles_where,
-                                dq_quantile_digest_where, dq_mutual_information_where */
+                                dq_quantile_digest_where, dq_mutual_information_where; dataset match:
+                                dq_freq_lookup_rows (which group a row hit), dq_rows_match (a row's other columns
+                                against the reference row of its group) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -921,6 +923,40 @@ dq_status dq_freq_unique_rows(const dq_freq_table* t, const int32_t* types, cons
 dq_status dq_freq_contains_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols,
                                 int64_t n_rows, const uint64_t* filter, uint64_t* contained, uint64_t* applies,
                                 void* hip_stream, int64_t* num_contained, int64_t* num_applies);
+/* Dataset match: does a row equal the reference table's row with the same key?  Two calls per chunk.
+ * dq_freq_lookup_rows is dq_freq_contains_rows that says WHICH group a row hit: group (device, n_rows int32, 4-byte
+ * aligned) receives for row r the index of its group in t's sorted keys (0 .. G-1; the keys ascend as unsigned 64-bit
+ * words -- an unhashed integer column's negative values after the others, a hashed table in hash order -- so the
+ * index is an identifier of the group, dq_freq_export's position, not a rank of the value) when the filter keeps the row,
+ * every key column is non-null and the tuple is a group of t, else -1.  The membership rule, the type rule, the
+ * DQ_E_STATE of a hashed table that is not self-contained and the by-value comparison of a found hash (a different
+ * tuple: -1, never the collision error) are dq_freq_contains_rows's: it is the same search.  *num_found (host,
+ * optional): the entries >= 0.  A table of more than 2^31 - 1 groups is DQ_E_UNSUPPORTED.  Arguments are checked
+ * before anything is launched, in dq_freq_contains_rows's order; n_rows = 0: DQ_OK, nothing written.
+ * dq_rows_match compares n_cols (1 .. 16) columns of the chunk with the reference's payload: payload row g
+ * (0 <= g < n_payload_rows) holds the compare columns of the reference row whose key is group g.  types / cols: the
+ * chunk's n_cols columns of n_rows rows; payload_types / payload: the payload's.  Column c of both must have the same
+ * type code (a decimal's precision and scale included) or both be string columns (UTF8 / LARGE_UTF8, in any pairing);
+ * any other difference -- DQ_TYPE_DICT_UTF8 included: decode it -- is DQ_E_INVALID naming the column and both codes.
+ * Outputs in the bitmap layout above (zero tail bits, 8-byte aligned, no byte past ceil(n_rows / 64) * 8 touched):
+ *   matched  bit r = 1 iff the filter (NULL: every row) keeps r, group[r] is a payload row, and every column is equal;
+ *   found    (NULL: not wanted) bit r = 1 iff the filter keeps r and group[r] is a payload row;
+ *   applies  (NULL: not wanted) bit r = 1 iff the filter keeps r.
+ * A group[r] < 0 or >= n_payload_rows is "not found" and addresses nothing.  Equality per column is null-safe:
+ * NULL equals NULL, NULL differs from every value, and the bytes under a NULL slot are never read.  Values compare as
+ * grouping keys do: fixed-width types by their value bits (every NaN the same, -0.0 and 0.0 distinct), BOOL by its
+ * bit, DECIMAL128 by its 16 bytes, strings by length and bytes.  *num_matched / *num_found / *num_applies (host,
+ * optional): the set bits; num_mismatch (host, n_cols entries, or NULL): entry c = the found rows whose column c
+ * differs -- with it every column of a found row is judged, without it a row stops at its first difference.
+ * n_rows < 2^31; n_rows = 0: DQ_OK, no bitmap written, the counts 0.  Arguments are checked before anything is
+ * launched.  Runs on `device`, enqueued on hip_stream, and synchronises it. */
+dq_status dq_freq_lookup_rows(const dq_freq_table* t, const int32_t* types, const dq_column_view* cols, int64_t n_rows,
+                              const uint64_t* filter, int32_t* group, void* hip_stream, int64_t* num_found);
+dq_status dq_rows_match(const int32_t* types, const dq_column_view* cols, const int32_t* payload_types,
+                        const dq_column_view* payload, int32_t n_cols, int64_t n_rows, int64_t n_payload_rows,
+                        const int32_t* group, const uint64_t* filter, uint64_t* matched, uint64_t* found,
+                        uint64_t* applies, int32_t device, void* hip_stream, int64_t* num_matched, int64_t* num_found,
+                        int64_t* num_applies, int64_t* num_mismatch);
 /* Row-level random split (the train / test split of suggestions/ConstraintSuggestionRunner.scala:127-148).  Row r of
  * the chunk has the global index g = row0 + r; h = XXH64 of g's 8 little-endian bytes under `seed`,
  * u = (h >> 11) * 2^-53, and the row is a test row iff u < test_ratio, else a training row: a pure function of

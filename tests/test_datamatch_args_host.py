@@ -1,0 +1,27 @@
+"""The argument validation of dq_freq_lookup_rows and dq_rows_match under ASan + UBSan, on the host.
+
+tests/datamatch_args_check.cpp, a stand-alone program with its own main, calls the two entries with every invalid
+argument that returns before the device is touched -- n_rows out of range, misaligned or NULL buffers, n_cols of 0 and
+17, type mismatches (no widening, a decimal's scale, a dictionary column) -- and checks status, message and that
+nothing was written.  The entries' host code (deequ_amd/csrc/dq_group.hip and what it links: dq_prim.hip,
+dq_freq_image.cpp) is compiled into the program with the host sanitizers, exactly as tests/test_refint_args_host.py
+builds its program; the kernels' device code is compiled as usual and never runs.  Nothing is loaded into Python."""
+import os
+import subprocess
+
+from tests.conftest import ROOT
+
+
+def test_lookup_and_match_argument_validation_sanitized(tmp_path):
+    csrc = os.path.join(ROOT, "deequ_amd", "csrc")
+    exe = tmp_path / "datamatch_args_check"
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-result",
+                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", str(exe),
+                    os.path.join(ROOT, "tests", "datamatch_args_check.cpp"), os.path.join(csrc, "dq_group.hip"),
+                    os.path.join(csrc, "dq_prim.hip"), os.path.join(csrc, "dq_freq_image.cpp")], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().splitlines()[-1].startswith("ok "), r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
