@@ -22,6 +22,7 @@ from .lengths import string_lengths  # noqa: F401
 from .grouping import (CountDistinct, Distinctness, Entropy, FrequenciesAndNumRows, Histogram,  # noqa: F401
                        MutualInformation, Uniqueness, UniqueValueRatio)
 from .matching import DatasetMatch, KeyedRows, KeySet, ReferentialIntegrity  # noqa: F401
+from .drift import DistributionDistance, ReferenceDistribution, StoredDistribution  # noqa: F401
 from .metrics import (DoubleMetric, Distribution, DistributionValue, Entity, HistogramMetric,  # noqa: F401
                       KeyedDoubleMetric)
 from .profiles import (ColumnProfiler, ColumnProfilerRunBuilder, ColumnProfilerRunner, ColumnProfiles,  # noqa: F401

@@ -199,6 +199,13 @@ class FreqSummary(ctypes.Structure):
                 ("entropy", ctypes.c_double)]
 
 
+class FreqDistanceResult(ctypes.Structure):
+    _fields_ = [("defined", ctypes.c_int32), ("linf_side", ctypes.c_int32), ("linf", ctypes.c_double),
+                ("tv", ctypes.c_double), ("js", ctypes.c_double), ("linf_key", ctypes.c_uint64),
+                ("n_common", ctypes.c_int64), ("n_only_a", ctypes.c_int64), ("n_only_b", ctypes.c_int64),
+                ("count_only_a", ctypes.c_int64), ("count_only_b", ctypes.c_int64)]
+
+
 class State(ctypes.Structure):
     _fields_ = [("op", ctypes.c_int32), ("has_value", ctypes.c_uint8 * 2), ("integral", ctypes.c_uint8),
                 ("reserved", ctypes.c_uint8), ("u", _StateUnion)]
@@ -342,6 +349,10 @@ def _load():
     L.dq_rows_match.argtypes = [P(c.c_int32), P(ColumnView), P(c.c_int32), P(ColumnView), c.c_int32, c.c_int64,
                                 c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32,
                                 c.c_void_p, P(c.c_int64), P(c.c_int64), P(c.c_int64), P(c.c_int64)]
+    L.dq_freq_distance.restype = c.c_int32
+    L.dq_freq_distance.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, P(FreqDistanceResult)]
+    L.dq_freq_ks.restype = c.c_int32
+    L.dq_freq_ks.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, P(c.c_double), P(c.c_int32)]
     L.dq_split_rows.restype = c.c_int32
     L.dq_split_rows.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_double, c.c_void_p, c.c_void_p, c.c_int32,
                                 c.c_void_p, P(c.c_int64), P(c.c_int64)]
@@ -503,6 +514,7 @@ EXPORTED = [
     "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
     "dq_row_max_outputs", "dq_row_program_create", "dq_row_program_info", "dq_row_program_destroy", "dq_row_outcomes",
     "dq_freq_unique_rows", "dq_freq_contains_rows", "dq_freq_lookup_rows", "dq_rows_match",
+    "dq_freq_distance", "dq_freq_ks",
     "dq_freq_build_where", "dq_freq_unique_rows_where", "dq_dict_count_where", "dq_bin_count_where",
     "dq_approx_quantiles_where", "dq_quantile_digest_where", "dq_mutual_information_where",
     "dq_pred_pool_num_exprs", "dq_pred_pool_expr", "dq_expr_eval", "dq_expr_eval_host",

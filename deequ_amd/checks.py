@@ -21,6 +21,7 @@ from .analyzers import DataType, DataTypeInstances
 from .grouping import (Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
 from .matching import DatasetMatch, ReferentialIntegrity
+from .drift import DistributionDistance
 from .quantiles import ApproxQuantile
 from .runner import AnalysisRunner, AnalyzerContext, arrow_data
 
@@ -301,6 +302,13 @@ class Check:  # Check.scala:59-902
         Check.doesDatasetMatch with matchColumnMappings.)"""
         return self._filterable(lambda w: _named(DatasetMatch(keyColumns, compareColumns, reference, w), assertion,
                                                  "DatasetMatchConstraint", None, hint))
+
+    def hasDistributionDistance(self, columns, reference, assertion, method="linf", binning=None, hint=None):
+        """The distance between the distribution of `columns` and `reference`'s (a drift.ReferenceDistribution) meets
+        the assertion; method: "linf" (upstream's Distance.categoricalDistance), "tv", "js" or "ks"; binning: a
+        binning.Bins the reference was built with.  NULL rows are part of neither distribution."""
+        return self._filterable(lambda w: _named(DistributionDistance(columns, reference, method, binning, w),
+                                                 assertion, "DistributionDistanceConstraint", None, hint))
 
     # ---- constraints on the grouping, histogram and quantile analyzers: filterable, the `where` is the analyzer's ----
     def isUnique(self, column, hint=None):  # Check.scala:139-141

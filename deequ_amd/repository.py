@@ -25,6 +25,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
 from .grouping import (CountDistinct, Distinctness, Entropy, Histogram, MutualInformation, Uniqueness, UniqueValueRatio,
                        _java_double_to_string)
 from .matching import DatasetMatch, ReferentialIntegrity, StoredKeyedRows, StoredKeySet
+from .drift import DistributionDistance, StoredDistribution
 from .metrics import (Distribution, DistributionValue, DoubleMetric, Entity, Failure, HistogramMetric,
                       KeyedDoubleMetric, MetricCalculationRuntimeException, Success)
 from .quantiles import ApproxQuantile, ApproxQuantiles
@@ -393,6 +394,15 @@ def _serialize_analyzer(analyzer: Analyzer) -> dict:
         return {"analyzerName": "DatasetMatch", "keyColumns": list(analyzer.keyColumns),
                 "compareColumns": [[c, rc] for c, rc in analyzer.mapping or ()], "where": analyzer.where,
                 "numKeys": int(analyzer.reference.num_keys)}
+    if t is DistributionDistance:
+        # (no upstream layout.)  The reference's table is not stored, only its numbers of groups and values
+        # (StoredDistribution): the analyzer comes back able to key stored metrics and refusing to run
+        from .binning import bins_to_json
+
+        return {"analyzerName": "DistributionDistance", "columns": list(analyzer.columns), "method": analyzer.method,
+                "where": analyzer.where,
+                "binning": None if analyzer.binning is None else bins_to_json(analyzer.binning),
+                "numGroups": int(analyzer.reference.num_groups), "numValues": int(analyzer.reference.num_values)}
     raise ValueError(f"Unable to serialize analyzer {analyzer}.")
 
 
@@ -430,6 +440,15 @@ def deserialize_analyzer(node: dict) -> Analyzer:  # AnalyzerDeserializer (:349-
     if name == "DatasetMatch":
         return DatasetMatch(list(node["keyColumns"]), [tuple(m) for m in node["compareColumns"]],
                             StoredKeyedRows(int(node["numKeys"])), where)
+    if name == "DistributionDistance":
+        binning = None
+        if node.get("binning") is not None:
+            from .binning import bins_from_json
+
+            binning = bins_from_json(node["binning"])
+        return DistributionDistance(list(node["columns"]),
+                                    StoredDistribution(int(node["numGroups"]), int(node["numValues"])),
+                                    node["method"], binning, where)
     raise ValueError(f"Unable to deserialize analyzer {name}.")
 
 

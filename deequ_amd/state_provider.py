@@ -50,7 +50,9 @@ def identifier(analyzer) -> str:
 
 
 def _has_frequency_state(analyzer) -> bool:
-    """A FrequencyBasedAnalyzer or a Histogram: its state is FrequenciesAndNumRows."""
+    """A FrequencyBasedAnalyzer (Uniqueness, Distinctness, CountDistinct, UniqueValueRatio, Entropy,
+    MutualInformation, and drift.DistributionDistance, binned or not) or a Histogram: its state is
+    FrequenciesAndNumRows."""
     from .grouping import FrequencyBasedAnalyzer, Histogram
 
     return isinstance(analyzer, (FrequencyBasedAnalyzer, Histogram))

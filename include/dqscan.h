@@ -52,7 +52,9 @@ extern "C" {
                                 dq_dict_count_where, dq_bin_count_where, dq_approx_quantiles_where,
                                 dq_quantile_digest_where, dq_mutual_information_where; dataset match:
                                 dq_freq_lookup_rows (which group a row hit), dq_rows_match (a row's other columns
-                                against the reference row of its group) */
+                                against the reference row of its group); distribution drift: dq_freq_distance
+                                (L-infinity / total variation / Jensen-Shannon between two frequency tables),
+                                dq_freq_ks (their two-sample Kolmogorov-Smirnov statistic) */
 
 typedef int32_t dq_status;
 #define DQ_OK 0
@@ -957,6 +959,52 @@ dq_status dq_rows_match(const int32_t* types, const dq_column_view* cols, const 
                         const int32_t* group, const uint64_t* filter, uint64_t* matched, uint64_t* found,
                         uint64_t* applies, int32_t device, void* hip_stream, int64_t* num_matched, int64_t* num_found,
                         int64_t* num_applies, int64_t* num_mismatch);
+/* Distribution drift: how far is the distribution of one frequency table from another's?  (Additions under ABI 6.)
+ * a is the data's table, b the reference's; both stay on the device and neither is changed.  N_a / N_b are the tables'
+ * n_values (the sums of their counts: NULL rows are part of neither distribution).  For a group g,
+ * p = (double)count_a(g) / (double)N_a and q likewise for b; a group a table lacks has probability 0 there.
+ * A group of a and a group of b are the same group when their key words are equal and, for hashed tables (strings,
+ * decimals, several columns), their stored tuples are equal by value -- string length and bytes, a decimal's 16 bytes,
+ * value bits otherwise: dq_freq_contains_rows' comparison.  Equal hashes with different tuples are two groups, one
+ * only in a and one only in b: never the collision error, never a match.  An unhashed table's key is its value's
+ * bits: every NaN one group, -0.0 and 0.0 two.
+ * dq_freq_distance, over the union of the groups:
+ *   linf = max |p - q|;  tv = 1/2 sum |p - q|;
+ *   js = 1/2 sum [p ln(p / m) + q ln(q / m)], m = (p + q) / 2, natural logarithm, a zero p (or q) contributing 0:
+ *        a value in [0, ln 2];
+ *   n_common / n_only_a / n_only_b: the groups in both tables, in a alone, in b alone; count_only_a / count_only_b:
+ *        the rows (counts) of a in groups b lacks, and of b in groups a lacks;
+ *   linf_key / linf_side: the key word of the group attaining linf and the table that holds its value (0 = a, also for
+ *        a group of both; 1 = b alone).  Ties go to the smaller unsigned key word, then to side a.
+ * Both tables must be self-contained (dq_freq_self_contained), else DQ_E_STATE.  They need the same number of columns
+ * and per column the same type code (a decimal's precision and scale are part of it; the string offset width is
+ * free); any other difference is DQ_E_INVALID naming the column and both codes; tables on different devices are
+ * DQ_E_INVALID.  All of that is checked before anything is launched.  Either table with n_values = 0: DQ_OK,
+ * defined = 0, every other member 0, nothing launched.
+ * Arithmetic is binary64 without contraction and with correctly rounded division: linf is bit for bit
+ * max |c_a / N_a - c_b / N_b| evaluated per group in IEEE doubles.  No floating-point atomics: a thread, a wave, a
+ * workgroup and one final pass sum in a fixed order that depends on the group counts alone, so two calls on the same
+ * tables return identical bits.  tv and js carry the roundings of their G terms (G = the union's size): within
+ * 16 (G + 1) 2^-53 of the exact sums.
+ * dq_freq_ks: the exact two-sample Kolmogorov-Smirnov statistic of two unhashed single-column tables of one type among
+ * F64 / F32 / I64 / I32 / I16 / I8 / DATE32 / TIMESTAMP; BOOL and every hashed table are DQ_E_UNSUPPORTED, different
+ * types DQ_E_INVALID.  Values order numerically; floats with -0.0 immediately below 0.0 (two groups, as the grouping
+ * has them), -inf and +inf in their numeric places and the canonical NaN greatest.  F_a(x) = (the counts of a's groups
+ * <= x, an exact integer) / N_a, one division; *ks = max over every group value x of either table of
+ * |F_a(x) - F_b(x)|, bit for bit that expression in IEEE doubles.  *defined = 0 (and *ks = 0) when either table has
+ * n_values = 0.  A table of more than 2^31 - 2 groups is DQ_E_UNSUPPORTED.
+ * Both run on the tables' device, enqueued on hip_stream, take their scratch from the grouping arena and synchronise
+ * the stream; nothing but the result goes to the host. */
+typedef struct dq_freq_distance_result {
+  int32_t defined;    /* 0: a table without values; everything below is 0 */
+  int32_t linf_side;  /* 0 = the linf group is a group of a, 1 = of b alone */
+  double linf, tv, js;
+  uint64_t linf_key;
+  int64_t n_common, n_only_a, n_only_b, count_only_a, count_only_b;
+} dq_freq_distance_result;
+dq_status dq_freq_distance(const dq_freq_table* a, const dq_freq_table* b, void* hip_stream,
+                           dq_freq_distance_result* out);
+dq_status dq_freq_ks(const dq_freq_table* a, const dq_freq_table* b, void* hip_stream, double* ks, int32_t* defined);
 /* Row-level random split (the train / test split of suggestions/ConstraintSuggestionRunner.scala:127-148).  Row r of
  * the chunk has the global index g = row0 + r; h = XXH64 of g's 8 little-endian bytes under `seed`,
  * u = (h >> 11) * 2^-53, and the row is a test row iff u < test_ratio, else a training row: a pure function of
