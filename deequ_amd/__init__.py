@@ -23,6 +23,8 @@ from .grouping import (CountDistinct, Distinctness, Entropy, FrequenciesAndNumRo
                        MutualInformation, Uniqueness, UniqueValueRatio)
 from .matching import DatasetMatch, KeyedRows, KeySet, ReferentialIntegrity  # noqa: F401
 from .drift import DistributionDistance, ReferenceDistribution, StoredDistribution  # noqa: F401
+from . import segments  # noqa: F401
+from .segments import (SegmentedAnalyzerContext, SegmentedVerificationResult, run_segmented)  # noqa: F401
 from .metrics import (DoubleMetric, Distribution, DistributionValue, Entity, HistogramMetric,  # noqa: F401
                       KeyedDoubleMetric)
 from .profiles import (ColumnProfiler, ColumnProfilerRunBuilder, ColumnProfilerRunner, ColumnProfiles,  # noqa: F401

@@ -132,6 +132,19 @@ class ColumnView(ctypes.Structure):
                 ("reserved", ctypes.c_int64)]
 
 
+class SegmentSlot(ctypes.Structure):
+    """dq_segment_slot: one (column view, type, op, filter bitmap) of a segmented scan."""
+    _fields_ = [("col", ColumnView), ("type", ctypes.c_int32), ("op", ctypes.c_int32), ("filter", ctypes.c_void_p)]
+
+
+SEG_COUNT, SEG_STATS = 1, 2  # enum dq_segment_op
+SEGMENT_MAX_SLOTS = 64       # DQ_SEGMENT_MAX_SLOTS
+# dq_segment_state as a numpy record
+SEGMENT_STATE_FIELDS = [("n", "f8"), ("mean", "f8"), ("m2", "f8"), ("sum", "f8"), ("isum", "i8"), ("count", "i8"),
+                        ("nan_count", "i8"), ("fmin", "f8"), ("fmax", "f8"), ("pinf_count", "i8"),
+                        ("ninf_count", "i8"), ("applies", "i8")]
+
+
 # RowLevelSchemaValidator column definitions (enum dq_schema_kind, dq_schema_column)
 SCHEMA_STRING, SCHEMA_INT, SCHEMA_DECIMAL, SCHEMA_TIMESTAMP = 1, 2, 3, 4
 
@@ -353,6 +366,12 @@ def _load():
     L.dq_freq_distance.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, P(FreqDistanceResult)]
     L.dq_freq_ks.restype = c.c_int32
     L.dq_freq_ks.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, P(c.c_double), P(c.c_int32)]
+    L.dq_segment_tile.restype = c.c_int32
+    L.dq_segment_tile.argtypes = []
+    L.dq_segment_order.restype = c.c_int32
+    L.dq_segment_order.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.dq_segment_scan.restype = c.c_int32
+    L.dq_segment_scan.argtypes = [P(SegmentSlot), c.c_int32, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p]
     L.dq_split_rows.restype = c.c_int32
     L.dq_split_rows.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_double, c.c_void_p, c.c_void_p, c.c_int32,
                                 c.c_void_p, P(c.c_int64), P(c.c_int64)]
@@ -514,7 +533,7 @@ EXPORTED = [
     "dq_utf8_length", "dq_utf8_length_host", "dq_dict_take_i32",
     "dq_row_max_outputs", "dq_row_program_create", "dq_row_program_info", "dq_row_program_destroy", "dq_row_outcomes",
     "dq_freq_unique_rows", "dq_freq_contains_rows", "dq_freq_lookup_rows", "dq_rows_match",
-    "dq_freq_distance", "dq_freq_ks",
+    "dq_freq_distance", "dq_freq_ks", "dq_segment_tile", "dq_segment_order", "dq_segment_scan",
     "dq_freq_build_where", "dq_freq_unique_rows_where", "dq_dict_count_where", "dq_bin_count_where",
     "dq_approx_quantiles_where", "dq_quantile_digest_where", "dq_mutual_information_where",
     "dq_pred_pool_num_exprs", "dq_pred_pool_expr", "dq_expr_eval", "dq_expr_eval_host",

@@ -535,6 +535,13 @@ class VerificationRunBuilder:  # VerificationRunBuilder.scala:28-149
         self.checks.append(getAnomalyCheck(self._metricsRepository, anomalyDetectionStrategy, analyzer, config))
         return self
 
+    def segmentBy(self, columns, maxSegments: int = 10000):
+        """The checks once per distinct tuple of `columns` (segments.run_segmented): a new builder whose run() gives a
+        SegmentedVerificationResult; more than maxSegments segments is a ValueError before any grouped launch."""
+        from .segments import SegmentedVerificationRunBuilder
+
+        return SegmentedVerificationRunBuilder(self.data, columns, maxSegments, self.checks, self.required)
+
     def run(self) -> VerificationResult:
         return VerificationSuite.doVerificationRun(self.data, self.checks, self.required, self._aggregateWith,
                                                    self._saveStatesWith, self._metricsRepository,

@@ -39,19 +39,29 @@ __device__ inline int64_t shift_group_start(const uint32_t* validity, const uint
 // alone, and the first with a finite selected value gives its mean (fixed butterfly order).  value(r): this
 // lane's value of row r as a double.  In the range's last group r runs past row1: value() must not read past
 // the range there, and what it returns is not used.  The pair pass passes range-local rows and pointers (row0 = 0).
+// The walk itself, over any `groups` 64-row groups: sel(g) the selection word of group g (wave-uniform), value(g)
+// this lane's value of its row of group g.  range_shift below is the walk over a contiguous row range; the segmented
+// scan (dq_segment.hip) walks the groups of a tile of gathered rows, whose selection words are ballots.
+template <typename S, typename V>
+__device__ __forceinline__ double groups_shift(int64_t groups, int64_t g0, S&& sel, V&& value) {
+  for (int64_t i = 0; i < groups; ++i) {
+    const int64_t g = g0 + i < groups ? g0 + i : g0 + i - groups;  // groups g0 .., then 0 .. g0 - 1
+    const uint64_t s = sel(g);
+    if (s == 0) continue;
+    const double x = value(g);
+    const uint64_t fm = __builtin_amdgcn_ballot_w64(__builtin_isfinite(x)) & s;
+    if (fm != 0) return wave_uniform(wave_sum_f64(lane_bit(fm) ? x : 0.0) / (double)__builtin_popcountll(fm));
+  }
+  return 0.0;
+}
+
 template <typename V>
 __device__ inline double range_shift(const uint32_t* validity, const uint32_t* mask, int64_t row0, int64_t row1, int lane,
                                      V&& value) {
   const int64_t groups = (row1 - row0 + 63) >> 6, g0 = (shift_group_start(validity, mask, row0, row1, lane) - row0) >> 6;
-  for (int64_t i = 0; i < groups; ++i) {
-    const int64_t r = row0 + 64 * (g0 + i < groups ? g0 + i : g0 + i - groups);  // groups g0 .., then 0 .. g0 - 1
-    const uint64_t sel = sel_word(validity, mask, r >> 5, row1 - r);
-    if (sel == 0) continue;
-    const double x = value(r + lane);
-    const uint64_t fm = __builtin_amdgcn_ballot_w64(__builtin_isfinite(x)) & sel;
-    if (fm != 0) return wave_uniform(wave_sum_f64(lane_bit(fm) ? x : 0.0) / (double)__builtin_popcountll(fm));
-  }
-  return 0.0;
+  return groups_shift(
+      groups, g0, [&](int64_t g) { return sel_word(validity, mask, (row0 + 64 * g) >> 5, row1 - (row0 + 64 * g)); },
+      [&](int64_t g) { return value(row0 + 64 * g + lane); });
 }
 
 }  // namespace dq

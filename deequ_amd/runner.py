@@ -581,6 +581,13 @@ class AnalysisRunBuilder:
         self._saveOrAppendResultsKey = resultKey
         return self
 
+    def segmentBy(self, columns, maxSegments=None):
+        """The analyzers once per distinct tuple of `columns` (segments.run_segmented): a new builder whose run() gives
+        a SegmentedAnalyzerContext.  State providers and the metrics repository are not part of a segmented run."""
+        from .segments import SegmentedAnalysisRunBuilder
+
+        return SegmentedAnalysisRunBuilder(self.data, columns, self.analyzers, maxSegments)
+
     def run(self) -> AnalyzerContext:
         return AnalysisRunner.doAnalysisRun(self.data, self.analyzers, self._aggregateWith, self._saveStatesWith,
                                             self._metricsRepository, self._reuseExistingResultsKey,

@@ -1005,6 +1005,47 @@ typedef struct dq_freq_distance_result {
 dq_status dq_freq_distance(const dq_freq_table* a, const dq_freq_table* b, void* hip_stream,
                            dq_freq_distance_result* out);
 dq_status dq_freq_ks(const dq_freq_table* a, const dq_freq_table* b, void* hip_stream, double* ks, int32_t* defined);
+/* Segmented metrics: the scan analyzers' states per group of a key column.  (Additions under ABI 6.)
+ * seg (device, n_rows int32) is dq_freq_lookup_rows' output against the key set of the segment columns: the row's
+ * segment 0 .. G - 1, or -1 for a row with a NULL key, which belongs to the trailing NULL segment G.
+ * dq_segment_order: perm (device, n_rows int32) receives the row numbers sorted stably by segment -- the rows of a
+ * segment ascend -- and offsets (device, G + 2 int64) the segments' first positions in perm; offsets[G + 1] = n_rows.
+ * n_rows < 2^31; n_rows = 0: DQ_OK, offsets all 0.  G + 1 beyond int32 is DQ_E_UNSUPPORTED.  Once per chunk, shared
+ * by every slot.
+ * dq_segment_scan: slots (host, 1 .. DQ_SEGMENT_MAX_SLOTS) over the G1 = G + 1 segments of perm / offsets; out
+ * (device, n_slots x G1 dq_segment_state, slot-major) receives per (slot, segment):
+ *   applies    the segment's rows the filter keeps (filter NULL: its rows);
+ *   count      of those, the rows whose validity bit is set (col.validity NULL: all of them);
+ * and for DQ_SEG_STATS (type F64 / F32 / I64 / I32 / I16 / I8 / DATE32 / TIMESTAMP; col.values not NULL) over those
+ * count rows what the column scan keeps for a column: n / mean / m2 (NaN values included, +-inf values counted in
+ * pinf_count / ninf_count instead), sum (floating types; without the +-inf values) or isum (integral types: the
+ * wrapping int64 sum), fmin / fmax over the values that are not NaN (v_min_f64 / v_max_f64: -0.0 below 0.0), nan_count.
+ * A segment without rows gets the empty state (n = 0, count = 0, fmin = +inf, fmax = -inf).  DQ_SEG_COUNT reads no
+ * value and ignores type.  The reduction is a function of offsets alone -- tiles of dq_segment_tile() rows from a
+ * segment's first row, each reduced in one order, merged in ascending tile order -- so equal inputs give equal bits;
+ * no floating-point atomics.  An unknown op or type, a NULL argument, n_slots or G1 out of range: DQ_E_INVALID before
+ * any launch; a valid type without segmented statistics (strings, BOOL, DECIMAL128): DQ_E_UNSUPPORTED.  Both calls
+ * run on the current device, enqueue on hip_stream and synchronise it. */
+#define DQ_SEGMENT_MAX_SLOTS 64
+#define DQ_SEGMENT_TILE 256
+enum dq_segment_op { DQ_SEG_COUNT = 1, DQ_SEG_STATS = 2 };
+typedef struct dq_segment_slot {
+  dq_column_view col;
+  int32_t type;            /* enum dq_type (DQ_SEG_STATS) */
+  int32_t op;              /* enum dq_segment_op */
+  const uint64_t* filter;  /* device bitmap of the chunk's rows (bit r = row r), or NULL: every row */
+} dq_segment_slot;
+typedef struct dq_segment_state {
+  double n, mean, m2, sum;
+  int64_t isum, count, nan_count;
+  double fmin, fmax;
+  int64_t pinf_count, ninf_count, applies;
+} dq_segment_state;
+int32_t dq_segment_tile(void);
+dq_status dq_segment_order(const int32_t* seg, int64_t n_rows, int64_t G, int32_t* perm, int64_t* offsets,
+                           void* hip_stream);
+dq_status dq_segment_scan(const dq_segment_slot* slots, int32_t n_slots, const int32_t* perm, const int64_t* offsets,
+                          int64_t G1, dq_segment_state* out, void* hip_stream);
 /* Row-level random split (the train / test split of suggestions/ConstraintSuggestionRunner.scala:127-148).  Row r of
  * the chunk has the global index g = row0 + r; h = XXH64 of g's 8 little-endian bytes under `seed`,
  * u = (h >> 11) * 2^-53, and the row is a test row iff u < test_ratio, else a training row: a pure function of
