@@ -1,22 +1,31 @@
-// dq_freq_table.h -- the frequency table (dq_freq_table) and the pieces that read it, shared by the translation units
-// that work on such tables: the grouping pass that builds, merges and probes them (dq_group.hip) and the comparison of
-// two of them (dq_dist.hip).  One copy of the chunk descriptor, of the value-bits rule (NaN canonical, -0.0 and 0.0
-// distinct), of the by-value tuple comparison, and of the scratch arena's helpers.
+// dq_freq_table.h -- the frequency table (dq_freq_table) and the pieces that read it, shared by the four translation
+// units that work on such tables: the grouping analyzers' build, MutualInformation, summary and top-N (dq_group.hip),
+// the table as a persisted state -- merge, value store, image (dq_freq_store.hip), the probes of other data's rows
+// against a table (dq_probe.hip) and the comparison of two tables (dq_dist.hip).  One copy of the chunk descriptor, of
+// the value-bits rule (NaN canonical, -0.0 and 0.0 distinct), of the row's validity, hash and key -- a probe hashes a
+// row exactly as the build hashed it, because both call these -- of the by-value tuple comparison, and of the scratch
+// arena's and the launches' host helpers.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <type_traits>
 #include <vector>
 
 #include "dq_arena.h"
+#include "dq_hash.h"
 #include "dq_hip_host.h"
 #include "dq_strkey.h"
 
 namespace dq {
 
 constexpr int kMaxGroupCols = 8;
+constexpr int kMaxGroupChunks = 4096;
+constexpr int kRowBits = 40;  // row id = chunk << 40 | row
+
+constexpr uint64_t kSeed2 = 0x9E3779B97F4A7C15ull;  // seed of the second (verification) tuple hash
 
 struct GroupCols {
   const void* values[kMaxGroupCols];
@@ -83,9 +92,44 @@ __device__ __forceinline__ bool tuple_equal_rows(const GroupCols& ga, const Grou
   return true;
 }
 
+__device__ __forceinline__ bool row_valid(const GroupCols& g, int64_t r) {
+  if (g.weight && g.weight[r] <= 0) return false;
+  for (int c = 0; c < g.n_cols; ++c)
+    if (g.validity[c] && !((g.validity[c][r >> 5] >> (r & 31)) & 1u)) return false;
+  return true;
+}
+
+// 64-bit hash of the row's tuple (columns in order; strings by bytes and length)
+inline __device__ uint64_t tuple_hash(const GroupCols& g, int64_t r, uint64_t seed = kSeed) {
+  uint64_t h = seed + XP5;
+  for (int c = 0; c < g.n_cols; ++c) {
+    if (g.type[c] == DQ_TYPE_UTF8 || g.type[c] == DQ_TYPE_LARGE_UTF8) {
+      const uint8_t* p;
+      int64_t len;
+      str_of(g, c, r, p, len);
+      h = mix_str(h, p, len);
+    } else if (is_dec(g.type[c])) {
+      const uint64_t* v = dec_at(g, c, r);
+      h = mix8(mix8(h, v[0]), v[1]);
+    } else {
+      h = mix8(h, value_bits(g, c, r));
+    }
+  }
+  return fmix64(h);
+}
+inline __device__ uint64_t tuple_key(const GroupCols& g, int64_t r) { return tuple_hash(g, r) & g.key_mask; }
+
+inline __device__ bool tuple_equal(const GroupCols* chunks, uint64_t ra, uint64_t rb) {
+  return tuple_equal_rows(chunks[ra >> kRowBits], chunks[rb >> kRowBits], (int64_t)(ra & ((1ull << kRowBits) - 1)),
+                          (int64_t)(rb & ((1ull << kRowBits) - 1)));
+}
+
 // the scratch of every grouping call (dq_arena.h): one arena for all translation units, defined in dq_group.hip
 using Frame = Arena<DeviceMem>::Frame;
 Arena<DeviceMem>& group_arena();
+
+// out[i] = i for i < n, enqueued on s (the kernel is dq_group.hip's: one copy for the units that number groups)
+dq_status fill_iota_u64(uint64_t* out, int64_t n, hipStream_t s);
 
 // out = the frame's next buffer, of `count` elements
 template <typename T> dq_status take(Frame& f, T*& out, size_t count) {
@@ -106,6 +150,21 @@ template <typename T> dq_status read_back(T* out, const void* src, hipStream_t s
   DQ_HIP(hipStreamSynchronize(s));
   return DQ_OK;
 }
+
+// *raised = the flag a kernel may have set: the flag's 8 bytes zeroed, `launch` enqueued, the flag read back
+template <typename Launch> dq_status read_flag(void* d_flag, hipStream_t s, int32_t* raised, Launch&& launch) {
+  DQ_HIP(hipMemsetAsync(d_flag, 0, 8, s));
+  launch();
+  DQ_HIP(hipGetLastError());
+  return read_back(raised, d_flag, s);
+}
+// f(std::true_type / std::false_type): a run-time bool as a template argument
+template <typename F> void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+inline int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(8192, (n + 255) / 256)); }
 
 // one column of a table's value store (owned: freed with it)
 struct StoreCol {
@@ -136,6 +195,22 @@ struct dq_freq_table {
 };
 
 namespace dq {
+
+// the chunk descriptor of one chunk's row of views (n_cols of them); a gather of non-null rows carries no validity
+inline GroupCols view_cols(const int32_t* types, int n_cols, const dq_column_view* row, uint64_t key_mask,
+                           bool with_validity) {
+  GroupCols g;
+  std::memset(&g, 0, sizeof(g));
+  g.n_cols = n_cols;
+  g.key_mask = key_mask;
+  for (int c = 0; c < n_cols; ++c) {
+    g.values[c] = row[c].values;
+    if (with_validity) g.validity[c] = reinterpret_cast<const uint32_t*>(row[c].validity);
+    g.offsets[c] = row[c].offsets;
+    g.type[c] = types[c];
+  }
+  return g;
+}
 
 // the chunk descriptor of a table's value store: group g's tuple is row g (strings have int64 offsets, a BOOL is a byte)
 inline GroupCols store_cols(const dq_freq_table* t) {

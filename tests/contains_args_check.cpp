@@ -1,7 +1,7 @@
-// contains_args_check.cpp -- the argument validation of dq_freq_contains_rows (deequ_amd/csrc/dq_group.hip) on the
+// contains_args_check.cpp -- the argument validation of dq_freq_contains_rows (deequ_amd/csrc/dq_probe.hip) on the
 // host, under ASan + UBSan: every combination of invalid arguments that returns before the device is touched.  The
 // entry checks, in this order and before any HIP call: n_rows, the bitmaps' alignment, NULL contained, NULL cols,
-// NULL table -- so none of these calls needs a table or a GPU.  A stand-alone program: dq_group.hip's host side is
+// NULL table -- so none of these calls needs a table or a GPU.  A stand-alone program: dq_probe.hip's host side is
 // compiled into it (tests/test_refint_args_host.py), dq::set_error is the one below, nothing is loaded into Python.
 #include <cstdarg>
 #include <cstdint>

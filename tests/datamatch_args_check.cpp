@@ -1,8 +1,8 @@
 // datamatch_args_check.cpp -- the argument validation of dq_freq_lookup_rows and dq_rows_match
-// (deequ_amd/csrc/dq_group.hip) on the host, under ASan + UBSan: every invalid argument that returns before the device
+// (deequ_amd/csrc/dq_probe.hip) on the host, under ASan + UBSan: every invalid argument that returns before the device
 // is touched.  dq_freq_lookup_rows checks in dq_freq_contains_rows's order (n_rows, alignment, NULL group / cols /
 // table); dq_rows_match checks n_cols, n_rows, n_payload_rows, alignment, NULL arguments, the types, the views'
-// buffers -- none of these calls needs a table or a GPU.  A stand-alone program: dq_group.hip's host side is compiled
+// buffers -- none of these calls needs a table or a GPU.  A stand-alone program: dq_probe.hip's host side is compiled
 // into it (tests/test_datamatch_args_host.py), dq::set_error is the one below, nothing is loaded into Python.
 #include <cstdarg>
 #include <cstdint>

@@ -6,8 +6,8 @@ The frequency table
 -------------------
 ``ref_table(cols, valid)`` counts the rows whose key columns are all non-null (FrequencyBasedAnalyzer.computeFrequencies,
 GroupingAnalyzers.scala:44-82).  A fixed-width value's key is its value bits under the rules of ``value_bits``
-(dq_group.hip:60-80): any f64 / f32 NaN becomes the canonical NaN, -0.0 and 0.0 stay distinct, integers are
-sign-extended to 64 bits, a bool is 0 or 1.  For one fixed-width column the table is what ``FreqTable.export()`` must
+(``fixed_bits`` in dq_freq_table.h): any f64 / f32 NaN becomes the canonical NaN, -0.0 and 0.0 stay distinct,
+integers are sign-extended to 64 bits, a bool is 0 or 1.  For one fixed-width column the table is what ``FreqTable.export()`` must
 return: the keys as uint64 in ascending unsigned order and their int64 counts.  Strings and tuples are grouped by a
 hash on the device, which this file does not predict: their counts come back as a sorted list (a multiset), together
 with each column's marginal counts.
@@ -16,8 +16,8 @@ Entropy and MutualInformation: value and bound
 ----------------------------------------------
 Both values are sums over the groups, evaluated with mpmath at 50 digits from the integer counts (ln of an integer is
 memoised, so a table of many groups with few distinct counts is cheap).  ``bound`` is the first-order bound of the
-rounding error of the double algorithm in ``summary_part`` / ``summary_final`` (dq_group.hip:321-349) and ``mi_part`` /
-``mi_final`` (:418-441), with u = 2**-53 the unit roundoff; every |delta| below is at most u.
+rounding error of the double algorithm in ``summary_part`` / ``summary_final`` and ``mi_part`` / ``mi_final``
+(dq_group.hip), with u = 2**-53 the unit roundoff; every |delta| below is at most u.
 
 Entropy, one group of count c among N rows, p = c / N, t = -p ln p.  The kernel computes
     ph = fl(c / N) = p (1 + d1)                      (c and N are exact doubles; the quotient is rounded once)
@@ -72,7 +72,7 @@ STRING = ("utf8", "large_utf8")
 
 
 def value_bits(dtype: str, values) -> np.ndarray:
-    """uint64 grouping key of every value of a fixed-width column (dq_group.hip:60-80)."""
+    """uint64 grouping key of every value of a fixed-width column (fixed_bits in dq_freq_table.h)."""
     if dtype == "f64":
         b = np.ascontiguousarray(values, dtype=np.float64).view(np.uint64).copy()
         b[(b & np.uint64(0x7FFFFFFFFFFFFFFF)) > np.uint64(0x7FF0000000000000)] = np.uint64(0x7FF8000000000000)

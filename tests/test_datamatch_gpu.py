@@ -14,7 +14,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-S = 2048          # kSplitters in deequ_amd/csrc/dq_group.hip: the splitters the lookup searches in LDS
+S = 2048          # kSplitters in deequ_amd/csrc/dq_probe.hip: the splitters the lookup searches in LDS
 MAX_GRID = 2048   # kMatchMaxGrid (and kContainsMaxGrid): workgroups of 4 waves, one 64-row word per wave and step
 I64_MIN, I64_MAX = -2 ** 63, 2 ** 63 - 1
 

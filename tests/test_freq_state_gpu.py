@@ -21,7 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-WAVE_COPY_LEN = 40  # dq_group.hip kWaveCopyLen: strings at least this long are copied by the whole wave
+WAVE_COPY_LEN = 40  # dq_freq_store.hip kWaveCopyLen: strings at least this long are copied by the whole wave
 LENGTHS = [0, 1, 3, 4, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, WAVE_COPY_LEN - 1, WAVE_COPY_LEN, WAVE_COPY_LEN + 1,
            1003]
 KINDS = {"utf8": ["utf8"], "large_utf8": ["large_utf8"], "decimal": ["decimal(20,4)"], "utf8_i32": ["utf8", "i32"],

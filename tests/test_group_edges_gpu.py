@@ -4,37 +4,37 @@ not reach.  Every case compares build_frequencies(...).frequencies.export() and 
 must be the reference's value bits in ascending order with its counts; for strings and tuples (hashed keys) the counts
 must be the reference's multiset.  Null slots carry non-zero payloads (every third one all-ones).
 
-What each block reaches (line numbers of dq_group.hip):
+What each block reaches (functions of dq_group.hip):
 
 * multi-tile compaction -- one chunk of 2048 * 2048 + 2048 + 1 rows.  The launch grid of group_compact is capped at
-  2048 workgroups of 2048 rows (:1061), so workgroup 0 loops to a full second tile, workgroup 1 to a tile of one row
+  2048 workgroups of 2048 rows (freq_build_impl), so workgroup 0 loops to a full second tile, workgroup 1 to a tile of one row
   (the last row) and no other workgroup loops: the tile loop and the reuse of wave_n / tile_base behind the barrier
-  at :227, and the carry of k_and / k_or across tiles (:200-201).  Unhashed keys ("w": ~50 000 wide values, the
-  dictionary form declines and the table is sorted; "r": values below 300, end_bit = 9) take the prefetch at :186 with
+  that ends a tile, and the carry of k_and / k_or across tiles.  Unhashed keys ("w": ~50 000 wide values, the
+  dictionary form declines and the table is sorted; "r": values below 300, end_bit = 9) take the prefetch (`fetch`) with
   its guard `t0 + tstride < n` true for exactly these two workgroups; row 2048 * 2048, the first row of the second
   tile, is the only row with its value and must come out as a group of count 1.  (One way to see that the test
   watches the prefetch: with `if (t0 + tstride < n)` replaced by `if (false)` in a scratch build, workgroup 0's second
   tile repeats its first tile's values and these cases fail.)  Hashed keys: ("l", "i") with ~3000 pairs -- more than
   kDictMax, so sorted also by default, then checked by verify_compacted with stride 2 in a second grid-stride
-  iteration (:293; grid_for caps at 8192 * 256 threads); ("d", "e") with 700 frequent pairs and no rare one takes the
-  dictionary form by default with two iterations of dict_count (:599; 2048 workgroups * 1024 keys) and must equal
+  iteration (grid_for caps at 8192 * 256 threads); ("d", "e") with 700 frequent pairs and no rare one takes the
+  dictionary form by default with two iterations of dict_count (2048 workgroups * 1024 keys) and must equal
   the sort's table; ("m", "j") with ~1.4 M pairs is checked in sorted order, verify_runs's second grid-stride
-  iteration (:259).  The unhashed tables cut into two chunks at 2048 * 2048 + 7 (the first chunk's workgroup 0 loops
+  iteration.  The unhashed tables cut into two chunks at 2048 * 2048 + 7 (the first chunk's workgroup 0 loops
   to a 7-row tile) must equal the one-chunk tables.
-* bit-range edges -- end_bit (:1076-1077) comes from the AND / OR of all appended keys: all keys equal (differ == 0,
+* bit-range edges -- end_bit (freq_build_impl) comes from the AND / OR of all appended keys: all keys equal (differ == 0,
   end_bit = 1), two keys differing in one bit b (end_bit = b + 1, the digit boundaries 8 / 16 / 24 / 32 / 48 and bit
   63 among them) under non-zero common high bits, 256 and 257 consecutive values above 1 << 40 (end_bit 8 and 9),
   sign-extended negative i32 / i8 among positive ones (end_bit = 64), 0.0 and -0.0 (bit 63 alone), NaNs of several
   payloads and signs (one canonical key), and a wide key that only one of two chunks holds, in both chunk orders
   (the AND / OR must accumulate across launches).
-* strided representative search -- verify_compacted's sample stride (:289-306) is above 1 only for more than 2048
+* strided representative search -- verify_compacted's sample stride is above 1 only for more than 2048
   groups: 5000 pairs (stride 3) and exactly 65 536 pairs in 530 000 rows (kCompactedMaxGroups and the
   8 * G <= nv edge, stride 32) must build without a collision report and with exact counts; 20 000 strings squeezed
   into 4096 hash keys (stride 2) must be refused as a collision.
 * ragged sizes -- row counts around a validity word, a wave, a block and a tile (31 .. 4097) with nulls forced at
   rows 0, 31, 32 and n - 1, a column without a validity bitmap, and an all-null column (nv == 0).
-* chunk shapes -- 64 chunks of 0 / 1 / 63 / 64 / 65 / 700 rows, zero-row chunks first, last and in between (:1060).
-* column limit -- kMaxGroupCols = 8 columns of eight types in one key; 9 are refused (:1007-1008).
+* chunk shapes -- 64 chunks of 0 / 1 / 63 / 64 / 65 / 700 rows, zero-row chunks first, last and in between (skipped by freq_build_impl).
+* column limit -- kMaxGroupCols = 8 columns of eight types in one key; 9 are refused (freq_build_impl).
 """
 from __future__ import annotations
 

@@ -174,7 +174,7 @@ def test_oracle_mutual_information_within_the_bound(name):
 
 
 def test_value_bits_rules():
-    """dq_group.hip:60-80: NaN canonical, -0.0 and 0.0 distinct, integers sign-extended, a bool 0 / 1."""
+    """fixed_bits in dq_freq_table.h: NaN canonical, -0.0 and 0.0 distinct, integers sign-extended, a bool 0 / 1."""
     nans = np.array([0x7FF8000000000000, 0xFFF8000000000000, 0x7FF0000000000001, 0xFFFFFFFFFFFFFFFF], dtype=np.uint64)
     assert set(R.value_bits("f64", nans.view(np.float64)).tolist()) == {0x7FF8000000000000}
     assert R.value_bits("f64", np.array([0.0, -0.0, np.inf])).tolist() == [0, 1 << 63, 0x7FF0000000000000]
